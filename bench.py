@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the Detectron2 detection hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rois uniform|clustered]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rois uniform|clustered] [--full] [--dump-outputs DIR]
                     [--workload maskrcnn_train|retinanet_100k|dcn_r50|maskrcnn_infer|rrpn_micro]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, `config`).  `--full` adds everything else to that line, each from runs of its own behind
+the timed region: `roofline`, `ops`, `ms_per_step_windows`, `roi_tiles`, `allreduce`, `cpu_baseline`, `extra_workloads`.
+`--dump-outputs DIR` writes what the LAST timed step computed as DIR/<name>.npy (see dump_outputs).
 
 `--gpus N` with N > 1 and no torchrun environment: bench.py launches itself as N ranks (one per GPU, RCCL) through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`; under torchrun it reads
@@ -48,9 +53,9 @@ dcn_r50 (configs[4]): the 13 ModulatedDeformConv (DCNv2) blocks of R50 res3-res5
 
 maskrcnn_infer, rrpn_micro: bench_extra.py (the inference chain as one HIP graph; the rotated operators).
 
-Extra JSON fields: `roofline` (dominant kernel, algorithmic bytes / flops over its HIP-event time), `cpu_baseline` (the
-oracle timed on this host), `ops` (per-op breakdown from a separate untimed pass), `extra_workloads` (the other workloads,
-a few steps each, in the default line).
+Extra JSON fields of `--full`: `roofline` (dominant kernel, algorithmic bytes / flops over its HIP-event time),
+`cpu_baseline` (the oracle timed on this host), `ops` (per-op breakdown from a separate untimed pass), `extra_workloads`
+(the other workloads, a few steps each, in the default line).
 """
 import argparse
 import ctypes
@@ -98,7 +103,13 @@ def parse(argv=None):
     ap.add_argument("--grad-allreduce", choices=["bf16", "fp32", "off"], default="bf16",
                     help="N > 1, maskrcnn_train: wire dtype of the gradient all-reduce (bf16 = the reference's "
                          "fp16_compress_hook idea, fp32 = plain DDP) or off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, behind the timed region: roofline kernel, "
+                         "per-op breakdown, more timing windows, the all-reduce alone, CPU baselines, the other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of the larger ones)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--disconnected", action="store_true",
                     help="maskrcnn_train: the round-2 step -- the ROI heads pool FIXED sampled lists and the RPN's "
                          "proposals feed nothing; two HIP graphs with one host sync between them.  Default: the "
@@ -127,6 +138,10 @@ def parse(argv=None):
             "rrpn_micro": (20, 20)}[a.workload]
     a.steps = dflt[0] if a.steps is None else a.steps
     a.warmup = dflt[1] if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.disconnected or a.plumbing_only):
+        ap.error("--dump-outputs: the --disconnected step and --plumbing-only hand no outputs to a caller")
     return a
 
 
@@ -390,6 +405,42 @@ def read_kernel_times(names):
         if cnt.value:
             out[kn] = (tot.value / cnt.value, cnt.value)
     return out
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: 64 MB in all, the .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy, float32 (float64 for 64-bit integer / float tensors), in the
+    tensor's logical (row-major) element order.  The budget is shared evenly: a tensor with more elements than its share
+    is written as a SAMPLE -- elements at `share` flat indices drawn by a generator seeded with 0, so that the same
+    elements are written by every run and every build (the indices depend on the sizes of the outputs alone)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    for name, t in arrays.items():
+        t = t.detach()
+        wide = t.dtype in (torch.int64, torch.float64)
+        share = DUMP_BUDGET_BYTES // max(len(arrays), 1) // (8 if wide else 4)
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = torch.randint(flat.numel(), (share,), generator=torch.Generator().manual_seed(0))
+            flat = flat[idx.to(flat.device)]
+        else:
+            flat = flat.reshape(t.shape)
+        np.save(os.path.join(path, name + ".npy"), flat.to(torch.float64 if wide else torch.float32).cpu().numpy())
+
+
+def train_step_outputs(w, out, loss):
+    """What a caller of the connected training step holds after it: the forward's results (connected_forward) and the
+    gradients the ONE backward pass left on the FPN features and the mask logits."""
+    labels, matches, counts = out["anchors"]
+    samp = out["sample"]
+    d = {"loss": loss, "mask_loss_stats": out["stats"], "anchor_labels": labels, "anchor_matches": matches,
+         "anchor_sample_counts": counts, "box_features": out["box_features"], "mask_features": out["mask_features"],
+         "mask_logits_grad": w.mask_logits.grad}
+    d.update({"sample_" + k: samp[k] for k in ("boxes", "classes", "gt_index", "index", "counts")})
+    d.update({f"feature_grad_p{i + 2}": f.grad for i, f in enumerate(w.feats)})
+    return d
 
 
 # ------------------------------------------------------------------------------------ maskrcnn_train
@@ -670,8 +721,9 @@ def roi_tile_histogram(w, out):
             "list_entries": entries, "rois": int(rois.shape[0] + head.shape[0])}
 
 
-def connected_step(w, t=None, grads=None):
-    """One eager pass of the connected step (per-op events when `t`), forward + ONE backward."""
+def connected_step(w, t=None, grads=None, keep_grads=False):
+    """One eager pass of the connected step (per-op events when `t`), forward + ONE backward.
+    keep_grads (--dump-outputs, last timed step): the gradients stay on the inputs for the caller to read."""
     from detectron2_amd.modeling import poolers as _poolers
 
     _poolers._NHWC_CACHE.clear()
@@ -685,10 +737,15 @@ def connected_step(w, t=None, grads=None):
     if grads is not None:
         run("allreduce_issue", lambda: [grads.reduce(i) for i in range(n_early, grads.num_buckets)])
         run("allreduce_wait", grads.finish)
+    if not keep_grads:
+        clear_input_grads(w)
+    return out
+
+
+def clear_input_grads(w):
     for f in w.feats:
         f.grad = None
     w.mask_logits.grad = None
-    return out
 
 
 class GraphedConnectedStep:
@@ -696,12 +753,21 @@ class GraphedConnectedStep:
     no host read anywhere in it.  N > 1: the graph is cut in front of the backward so that the ROI heads' gradient
     bucket can be handed to RCCL there (two launches, still no host sync)."""
 
-    def __init__(self, w, grads):
+    def __init__(self, w, grads, keep_outputs=False):
+        """keep_outputs (--dump-outputs): `.outputs` = the forward's results, detached, at the addresses every replay
+        rewrites (by default only the loss and the gradients on the inputs outlive the capture)."""
         self.w, self.grads = w, grads
         self.split = grads is not None
+        self.outputs = None
 
         def fwd():
             self.out = connected_forward(w)
+            if keep_outputs:
+                det = lambda v: v.detach() if torch.is_tensor(v) else v  # noqa: E731
+                self.outputs = {"anchors": tuple(det(v) for v in self.out["anchors"]), "stats": det(self.out["stats"]),
+                                "sample": {k: det(v) for k, v in self.out["sample"].items() if k != "_hold"},
+                                "box_features": det(self.out["box_features"]),
+                                "mask_features": det(self.out["mask_features"])}
             return self.out["loss"].detach()
 
         def bwd():
@@ -1050,17 +1116,63 @@ def bench_maskrcnn(args, ctx):
     KERN = "pool_bwd_staged_r7"
     KERN_SEL = "pool_bwd_pair,pool_bwd_staged_r7"  # the paired tile gather (both poolers, one launch) when the chain takes it
     use_graph = not args.no_graph
+    dump = args.dump_outputs if rank == 0 else None
     if use_graph:
-        gstep = GraphedConnectedStep(w, grads) if w.connected else GraphedStep(w, grads)
+        gstep = GraphedConnectedStep(w, grads, keep_outputs=bool(dump)) if w.connected else GraphedStep(w, grads)
         for _ in range(3):
             gstep()
         sw.start()
         for _ in range(args.steps):
-            gstep()
+            loss = gstep()
         elapsed = sw.stop()
+        if dump:  # (the graph's outputs live at fixed addresses: they hold the last replay's results)
+            dump_outputs(dump, train_step_outputs(w, gstep.outputs, loss))
+    else:
+        _dc.lib().d2amd_timing_select(KERN_SEL.encode())  # HIP events around the roofline kernel only, in the timed region
+        dom_timer = Timer(only=("backward",))
+        sw.start()
+        for i in range(args.steps):
+            last = step(w, dom_timer, grads, **({"keep_grads": True} if dump and i == args.steps - 1 else {}))
+        elapsed = sw.stop()
+        if dump:
+            dump_outputs(dump, train_step_outputs(w, last, last["loss"]))
+            clear_input_grads(w)
+        allreduce_info = None
+    ms_step = elapsed / args.steps * 1e3
+    windows = [ms_step]
+    out = {
+        "metric": "img/s through the Mask R-CNN R50-FPN detection hot path (training ops), 1333x800 bs=2/GPU",
+        "value": round(world * w.n_img * args.steps / elapsed, 2), "unit": "img/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "maskrcnn_r50fpn_train_hotpath_bs2_800x1344 (BASELINE configs[1]; configs[2] at n_gpus 8)",
+                   "layout": args.layout, "global_batch": world * w.n_img,
+                   "rois": w.rois_mode + (" (a trained RPN's picture: proposals and positives clustered on the 16 GT boxes)"
+                                          if w.rois_mode == "clustered" else " (random RPN head: proposals spread over the image)"),
+                   "step": ("connected: RPN selection + NMS -> label_and_sample_proposals on the NMS's device-side counts -> "
+                            "box pooler on the 512 sampled rows / image, mask pooler + targets + masked loss on their "
+                            "first 128 rows (both poolers as ONE launch per direction: pool_pair_rois / "
+                            "d2amd_roi_pooler_backward_pair); anchor labelling + sampling beside the NMS; no host read inside "
+                            "the step"
+                            if w.connected else "disconnected (round 2): fixed ROI lists, the RPN's proposals feed nothing"),
+                   "launch": (("ONE HIP graph per step (one hipGraphLaunch, no host sync)" if grads is None else
+                               "2 HIP graphs per step (forward | backward, cut for the gradient all-reduce), no host sync")
+                              if use_graph and w.connected else
+                              "2 HIP graphs per step (RPN half | ROI-head half + backward), one host sync between them"
+                              if use_graph else "eager: every op launched from Python"),
+                   "streams": ("independent branches forked onto side streams (anchor labelling + sampling beside the NMS; "
+                               "both poolers | mask targets + loss), joined before the backward"
+                               if w.overlap else "one stream"),
+                   "parallelism": f"dp{world}: images sharded, no data-path collective; "
+                                  + (grads_description(grads) if grads is not None else
+                                     "no gradient all-reduce (world size 1, like DDP)")},
+    }
+    if not args.full:  # a plain run ends here: everything below takes runs of its own
+        _dc.lib().d2amd_timing_select(None)
+        return out if rank == 0 else None
+    if use_graph:
         # The contract's timed region is the window above (`value` / `ms_per_step`).  Boxes differ by +-7 % and a window
         # is ~0.1 s: four more windows of the same K steps give the spread printed beside it (`ms_per_step_windows`).
-        windows = [elapsed / args.steps * 1e3]
         if world == 1:
             for _ in range(4):
                 sw.start()
@@ -1075,15 +1187,6 @@ def bench_maskrcnn(args, ctx):
         for _ in range(args.steps):
             step(w, dom_timer, grads)
         torch.cuda.synchronize()
-    else:
-        _dc.lib().d2amd_timing_select(KERN_SEL.encode())  # HIP events around the roofline kernel only, in the timed region
-        dom_timer = Timer(only=("backward",))
-        sw.start()
-        for _ in range(args.steps):
-            step(w, dom_timer, grads)
-        elapsed = sw.stop()
-        allreduce_info = None
-        windows = [elapsed / args.steps * 1e3]
     ktimes = read_kernel_times(KERN_SEL.split(","))
     paired = "pool_bwd_pair" in ktimes
     if paired:
@@ -1160,40 +1263,16 @@ def bench_maskrcnn(args, ctx):
                 "alg_bytes_per_launch": int(per), "ms_per_launch": round(dom_ms_timed, 4),
                 "timing": "HIP events on the launch stream around the op, mean over the timed steps",
                 "kernels_ms": {k: round(v[0], 4) for k, v in ktimes.items()}}
-    out = {
-        "metric": "img/s through the Mask R-CNN R50-FPN detection hot path (training ops), 1333x800 bs=2/GPU",
-        "value": round(world * w.n_img * args.steps / elapsed, 2), "unit": "img/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+    out["config"]["ops_per_step"] = counts
+    out.update({
         "ms_per_step_windows": {"n": len(windows), "min": round(min(windows), 4),
                                 "median": round(sorted(windows)[len(windows) // 2], 4), "max": round(max(windows), 4),
                                 "note": "windows of `steps` replays each; the first one is the contract's timed region "
                                         "(`value`, `ms_per_step`)"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "maskrcnn_r50fpn_train_hotpath_bs2_800x1344 (BASELINE configs[1]; configs[2] at n_gpus 8)",
-                   "layout": args.layout, "global_batch": world * w.n_img, "ops_per_step": counts,
-                   "rois": w.rois_mode + (" (a trained RPN's picture: proposals and positives clustered on the 16 GT boxes)"
-                                          if w.rois_mode == "clustered" else " (random RPN head: proposals spread over the image)"),
-                   "step": ("connected: RPN selection + NMS -> label_and_sample_proposals on the NMS's device-side counts -> "
-                            "box pooler on the 512 sampled rows / image, mask pooler + targets + masked loss on their "
-                            "first 128 rows (both poolers as ONE launch per direction: pool_pair_rois / "
-                            "d2amd_roi_pooler_backward_pair); anchor labelling + sampling beside the NMS; no host read inside "
-                            "the step"
-                            if w.connected else "disconnected (round 2): fixed ROI lists, the RPN's proposals feed nothing"),
-                   "launch": (("ONE HIP graph per step (one hipGraphLaunch, no host sync)" if grads is None else
-                               "2 HIP graphs per step (forward | backward, cut for the gradient all-reduce), no host sync")
-                              if use_graph and w.connected else
-                              "2 HIP graphs per step (RPN half | ROI-head half + backward), one host sync between them"
-                              if use_graph else "eager: every op launched from Python"),
-                   "streams": ("independent branches forked onto side streams (anchor labelling + sampling beside the NMS; "
-                               "both poolers | mask targets + loss), joined before the backward"
-                               if w.overlap else "one stream"),
-                   "parallelism": f"dp{world}: images sharded, no data-path collective; "
-                                  + (grads_description(grads) if grads is not None else
-                                     "no gradient all-reduce (world size 1, like DDP)")},
         "roofline": roof, "gpu_ms_per_step_sum_of_ops": round(sum(v["ms_per_step"] for v in ops.values()), 4),
         "ops": ops,
         "ops_note": f"per-op times: separate untimed pass of {bsteps} steps with HIP events around every op",
-    }
+    })
     if w.connected:
         try:  # (diagnostic: the distribution the tile gather worked on; one eager step after everything timed)
             out["roi_tiles"] = roi_tile_histogram(w, connected_step(w))
@@ -1333,12 +1412,16 @@ def bench_retinanet(args, ctx):
     for _ in range(args.steps):
         res = one()
     elapsed = sw.stop()
-    if graphed:  # a replayed graph has no per-kernel events: an eager pass of the same steps right after the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {f"image{i}_{k}": v for i, r in enumerate(res) for k, v in
+                                         (("pred_boxes", r.pred_boxes.tensor), ("scores", r.scores),
+                                          ("pred_classes", r.pred_classes))})
+    if graphed and args.full:  # a replayed graph has no per-kernel events: an eager pass of the same steps right after the timed region
         _dc.lib().d2amd_timing_select(",".join(knames).encode())
         for _ in range(args.steps):
             dense_detector_inference_fused(anchors, logits, deltas, sizes, 0.0, RETINA_TOPK, RETINA_NMS, RETINA_MAXDET)
         torch.cuda.synchronize()
-    ktimes = read_kernel_times(knames)
+    ktimes = read_kernel_times(knames) if args.full else {}
     _dc.lib().d2amd_timing_select(None)
     if rank != 0:
         return None
@@ -1385,9 +1468,10 @@ def bench_retinanet(args, ctx):
                    "num_classes": RETINA_K, "topk_candidates": RETINA_TOPK, "score_thresh": 0.0, "nms_thresh": RETINA_NMS,
                    "detections_kept": [len(r) for r in res], "global_batch": world * n_img, "execution": execution,
                    "parallelism": f"dp{world}: images sharded, replicas only (inference, no collective)"},
-        "roofline": roof,
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        out["roofline"] = roof
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_retinanet(anchors, logits, deltas)
     return out
 
@@ -1435,11 +1519,17 @@ def bench_dcn(args, ctx):
             blocks.append((tag, mod, x.requires_grad_(True), off.requires_grad_(True), msk.requires_grad_(True), gy))
             flops_fwd += 2.0 * ch * ch * 9 * n_img * h * wd
 
+    kept = {}  # --dump-outputs: every block's output and gradients of the last call (in a captured step: of the last replay)
+
     def one(t=None):
         run = (lambda name, fn: t.run(name, fn)) if t is not None else (lambda name, fn: fn())
-        for tag, mod, x, off, msk, gy in blocks:
+        for i, (tag, mod, x, off, msk, gy) in enumerate(blocks):
             y = run("fwd_" + tag, lambda: mod(x, off, msk))
             run("bwd_" + tag, lambda: torch.autograd.backward([y], [gy]))
+            if args.dump_outputs:
+                kept.update({f"block{i:02d}_{tag}_{k}": v for k, v in (
+                    ("y", y.detach()), ("grad_x", x.grad), ("grad_offset", off.grad), ("grad_mask", msk.grad),
+                    ("grad_weight", mod.weight.grad))})
             x.grad = off.grad = msk.grad = mod.weight.grad = None
 
     # The step is ~400 launches through Python and autograd (13 x (forward + backward)): issued eagerly it is as much a
@@ -1465,15 +1555,17 @@ def bench_dcn(args, ctx):
     for _ in range(args.steps):
         step()
     elapsed = sw.stop()
-    if graphed:  # a replayed graph has no per-kernel events: an eager pass right after the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kept)
+    if graphed and args.full:  # a replayed graph has no per-kernel events: an eager pass right after the timed region
         _dc.lib().d2amd_timing_select(",".join(knames).encode())
         for _ in range(min(args.steps, 10)):
             one()
         torch.cuda.synchronize()
-    ktimes = read_kernel_times(knames)
+    ktimes = read_kernel_times(knames) if args.full else {}
     _dc.lib().d2amd_timing_select(None)
     timer = Timer()
-    bsteps = min(args.steps, 5)
+    bsteps = min(args.steps, 5) if args.full else 0
     for _ in range(bsteps):
         one(timer)
     torch.cuda.synchronize()
@@ -1532,10 +1624,11 @@ def bench_dcn(args, ctx):
                    "layout": args.layout if dtype != torch.float32 else "nchw", "global_batch": world * n_img,
                    "gflop_per_step": round(3 * flops_fwd / 1e9, 1), "execution": execution,
                    "parallelism": f"dp{world}: images sharded; DCN weight gradients reduce with the model's (not in this step)"},
-        "roofline": roof, "ops": ops,
         "step_tflops": round(3 * flops_fwd / 1e12 / (elapsed / args.steps), 1),
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        out.update({"roofline": roof, "ops": ops})
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_dcn(blocks)
     return out
 
@@ -1647,9 +1740,11 @@ def main():
         # The default run also carries BASELINE configs[3] and [4] and the two SURVEY 8(d) workloads of bench_extra.py (a
         # few steps each, no CPU leg) so that the driver's ONE line records them: `extra_workloads` = their own metric /
         # value / ms_per_step / roofline.
-        if args.workload == "maskrcnn_train" and world == 1 and not args.no_extra_workloads and not args.force_dist:
+        if (args.full and args.workload == "maskrcnn_train" and world == 1 and not args.no_extra_workloads
+                and not args.force_dist):
             import copy
 
+            args.dump_outputs = None  # (written above, by the headline workload; the short runs below copy `args`)
             extra = {}
             # (steps / warm-up: a single slow step of 10 moved dcn_r50 from 3.3 to 4.7 ms on one box: 20-50 steps, 10-20 warm)
             for name, fn, steps, warm in (("retinanet_100k", bench_retinanet, 50, 20), ("dcn_r50", bench_dcn, 20, 10),
@@ -1695,7 +1790,7 @@ def main():
                     "dcn_r50_nchw_ms": extra["dcn_r50_nchw"].get("ms_per_step"),
                     "clustered_rois_ms": extra["clustered_rois"].get("ms_per_step")}
             out.update({k: v for k, v in flat.items() if v is not None})
-        if args.workload == "maskrcnn_train":
+        if args.workload == "maskrcnn_train" and args.full and rank == 0:
             km = (out.get("roofline") or {}).get("kernels_ms") or {}
             for key, name in (("pool_bwd_pair_us", "pool_bwd_pair"), ("pool_fwd_pair_us", "pool_fwd_pair")):
                 if name in km:

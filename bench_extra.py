@@ -219,14 +219,18 @@ def bench_maskrcnn_infer(args, ctx):
         for _ in range(args.steps):
             out = run_step(w)
         elapsed = sw.stop()
-        if graphed:  # (a replayed graph has no per-kernel events: an eager pass of the synchronous chain right after)
+        if args.dump_outputs and rank == 0:
+            B.dump_outputs(args.dump_outputs, {f"image{i}_{k}": v for i, d in enumerate(out["detections"]) for k, v in
+                                               (("pred_boxes", d[0]), ("scores", d[1]), ("pred_classes", d[2]),
+                                                ("pred_masks", out["masks"][i]))})
+        if graphed and args.full:  # (a replayed graph has no per-kernel events: an eager pass of the synchronous chain right after)
             for _ in range(min(args.steps, 10)):
                 infer_step(w)
             torch.cuda.synchronize()
-        ktimes = B.read_kernel_times(knames)
+        ktimes = B.read_kernel_times(knames) if args.full else {}
         _dc.lib().d2amd_timing_select(None)
         t = B.Timer()
-        for _ in range(min(args.steps, 10)):
+        for _ in range(min(args.steps, 10) if args.full else 0):
             infer_step(w, t.run)
         torch.cuda.synchronize()
     if rank != 0:
@@ -261,9 +265,10 @@ def bench_maskrcnn_infer(args, ctx):
                    "paste_size": [ORIG_H, ORIG_W], "execution": execution or ("eager; box-head inference per image as the reference (A/B)" if INFER_LOOP else
                                  "eager; box-head inference fused over the batch (2 host syncs), the other syncs where the reference has them"),
                    "parallelism": f"dp{world}: images sharded, replicas only (inference, no collective)"},
-        "roofline": roof,
-        "ops": {k: {"ms_per_step": round(v, 4)} for k, v in t.totals_ms().items()},
     }
+    if not args.full:
+        return res
+    res.update({"roofline": roof, "ops": {k: {"ms_per_step": round(v, 4)} for k, v in t.totals_ms().items()}})
     for k, v in res["ops"].items():
         v["ms_per_step"] = round(v["ms_per_step"] / max(min(args.steps, 10), 1), 4)
     if not args.no_cpu_baseline and world == 1:
@@ -353,10 +358,15 @@ def bench_rrpn_micro(args, ctx):
     for _ in range(args.steps):
         iou, keep, y = rrpn_step(w)
     elapsed = sw.stop()
-    ktimes = B.read_kernel_times(knames)
+    if args.dump_outputs and rank == 0:
+        arrays = {"roi_align_rotated": y}
+        for i in range(len(ids)):
+            arrays.update({f"image{i}_iou_rotated": iou[i], f"image{i}_nms_rotated_keep": keep[i]})
+        B.dump_outputs(args.dump_outputs, arrays)
+    ktimes = B.read_kernel_times(knames) if args.full else {}  # (events of the timed steps: this workload runs eagerly)
     _dc.lib().d2amd_timing_select(None)
     t = B.Timer()
-    for _ in range(min(args.steps, 10)):
+    for _ in range(min(args.steps, 10) if args.full else 0):
         rrpn_step(w, t.run)
     torch.cuda.synchronize()
     if rank != 0:
@@ -393,9 +403,11 @@ def bench_rrpn_micro(args, ctx):
                    "global_batch": world * n_img, "iou_pairs_per_image": pairs_iou, "nms_boxes_per_image": sum(per),
                    "nms_kept": [int(k.shape[0]) for k in keep], "rotated_rois": int(sum(r.shape[0] for r in w.rot_rois)),
                    "parallelism": f"dp{world}: images sharded, replicas only"},
-        "roofline": roof,
-        "ops": {k: {"ms_per_step": round(v / max(min(args.steps, 10), 1), 4)} for k, v in t.totals_ms().items()},
     }
+    if not args.full:
+        return res
+    res.update({"roofline": roof,
+                "ops": {k: {"ms_per_step": round(v / max(min(args.steps, 10), 1), 4)} for k, v in t.totals_ms().items()}})
     if not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline_rrpn(w)
     return res

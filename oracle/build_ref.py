@@ -26,8 +26,8 @@ SOURCES = [
 
 # The reference's own PYTHON modules that tests run (the callers of the hot path: SURVEY 8 row g1 -- poolers.py,
 # proposal_utils.py, mask_head.py, mask_ops.py, structures/masks.py and what they need).  Byte-compiled where they lie
-# into oracle/_ref/py/*.pyc -- a build product like libd2ref.so, git-ignored, never the source -- so that the GPU box,
-# which has no /root/reference, can load them (oracle/ref.py: _load_by_path falls back to the .pyc).
+# into oracle/_ref/py/*.pybc -- a build product like libd2ref.so, git-ignored, never the source -- so that a machine
+# without the reference tree can load them (oracle/ref.py: _load_by_path falls back to the bytecode).
 PY_MODULES = [
     "detectron2/layers/mask_ops.py", "detectron2/structures/boxes.py", "detectron2/structures/instances.py",
     "detectron2/structures/masks.py", "detectron2/modeling/matcher.py", "detectron2/modeling/sampling.py",
@@ -43,10 +43,14 @@ PY_MODULES = [
     "tests/structures/test_boxes.py", "tests/modeling/test_roi_pooler.py", "tests/modeling/test_matcher.py",
 ]
 PY_OUT = os.path.join(OUT_DIR, "py")
+# The staged bytecode is NOT named *.pyc: that suffix marks caches, which whatever copies or cleans a tree is free to
+# drop because Python rebuilds them from the source -- and these files have no source wherever the reference tree is
+# absent.  SourcelessFileLoader reads the pyc format under any name.
+BYTECODE_SUFFIX = ".pybc"
 
 
 def pyc_path(relpath):
-    return os.path.join(PY_OUT, relpath.replace("/", "__") + "c")
+    return os.path.join(PY_OUT, os.path.splitext(relpath.replace("/", "__"))[0] + BYTECODE_SUFFIX)
 
 
 def build_py(force=False):
@@ -65,16 +69,26 @@ def build_py(force=False):
 
 
 # The reference's WHOLE Python package (detectron2/**/*.py, 156 files), byte-compiled where it lies into
-# oracle/_ref/pkg/detectron2/**/*.pyc -- sourceless modules the standard import machinery loads once oracle/_ref/pkg is
-# on sys.path.  tests/_reference_model.py imports the reference's GeneralizedRCNN / RetinaNet / DeformBottleneckBlock
+# oracle/_ref/pkg/detectron2/**/*.pybc -- sourceless modules the import machinery loads once oracle/_ref/pkg is on
+# sys.path and pkg_path_hook in sys.path_hooks.  tests/_reference_model.py imports the reference's GeneralizedRCNN / RetinaNet / DeformBottleneckBlock
 # from it (SURVEY 8 row g: the models load unchanged); third-party packages the image lacks are stubbed there.
 PKG_OUT = os.path.join(OUT_DIR, "pkg")
+
+
+def pkg_path_hook(path):
+    """sys.path_hooks entry: directories of the bytecode tree get a finder that knows BYTECODE_SUFFIX as a sourceless
+    module; every other path is left to the standard hooks."""
+    import importlib.machinery as im
+
+    if os.path.commonpath([os.path.abspath(path), PKG_OUT]) != PKG_OUT or not os.path.isdir(path):
+        raise ImportError(path)
+    return im.FileFinder(path, (im.SourcelessFileLoader, [BYTECODE_SUFFIX]))
 
 
 def build_pkg(force=False):
     """-> True if the bytecode tree exists."""
     root = os.path.join(REF, "detectron2")
-    marker = os.path.join(PKG_OUT, "detectron2", "__init__.pyc")
+    marker = os.path.join(PKG_OUT, "detectron2", "__init__" + BYTECODE_SUFFIX)
     if not os.path.isdir(root):
         return os.path.exists(marker)
     import py_compile
@@ -86,7 +100,7 @@ def build_pkg(force=False):
             if not f.endswith(".py"):
                 continue
             src = os.path.join(d, f)
-            dst = os.path.join(PKG_OUT, os.path.relpath(src, REF)) + "c"
+            dst = os.path.join(PKG_OUT, os.path.splitext(os.path.relpath(src, REF))[0]) + BYTECODE_SUFFIX
             if force or not os.path.exists(dst) or os.path.getmtime(dst) < os.path.getmtime(src):
                 os.makedirs(os.path.dirname(dst), exist_ok=True)
                 py_compile.compile(src, cfile=dst, doraise=True, invalidation_mode=py_compile.PycInvalidationMode.UNCHECKED_HASH)

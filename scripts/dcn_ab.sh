@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests/test_gpu_dcn_tc.py tests/test_gpu_dcn_refere
 NAMES=""
 for V in "$@"; do
   name=${V%%:*}; kv=${V#*:}; NAMES="$NAMES $name"
-  env "$kv" timeout 300 python bench.py --workload dcn_r50 --no-cpu-baseline > $OUT/bench_dcn_$name.json 2> $OUT/bench_dcn_$name.err
+  env "$kv" timeout 300 python bench.py --full --workload dcn_r50 --no-cpu-baseline > $OUT/bench_dcn_$name.json 2> $OUT/bench_dcn_$name.err
 done
 python - $NAMES <<PY
 import json, sys

@@ -1,7 +1,7 @@
 #!/bin/bash
-# The driver's line (python bench.py) on the box, summarised.  $1 = tag under gpurun_out/r05/
+# The complete default line (python bench.py --full) on the GPU machine, summarised.  $1 = tag of the files under $OUT
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; TAG=${1:-default}; OUT=gpurun_out/r05; mkdir -p $OUT
-timeout 900 python bench.py ${@:2} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "rc=$?"; tail -3 $OUT/bench_$TAG.err
+timeout 900 python bench.py --full ${@:2} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "rc=$?"; tail -3 $OUT/bench_$TAG.err
 python - <<PY
 import json
 d=json.load(open("$OUT/bench_$TAG.json"))

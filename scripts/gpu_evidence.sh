@@ -8,9 +8,9 @@ rocm-smi --showproductname 2>/dev/null | head -8 > $OUT/gpu.txt; nproc >> $OUT/g
 timeout 300 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
 D2AMD_DUMP_RATIOS=$OUT/parity_margins.json D2AMD_REFERENCE_TEST_REPORT=$OUT/reference_tests_report.txt timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.log
 for WL in maskrcnn_infer rrpn_micro retinanet_100k dcn_r50; do
-  timeout 600 python bench.py --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err; echo "$WL rc=$?"
+  timeout 600 python bench.py --full --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err; echo "$WL rc=$?"
 done
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default rc=$?"; cut -c1-260 $OUT/bench_default.json
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default rc=$?"; cut -c1-260 $OUT/bench_default.json
 python - <<PY
 import json
 for n in ("default","maskrcnn_infer","rrpn_micro","retinanet_100k","dcn_r50"):
@@ -20,6 +20,6 @@ for n in ("default","maskrcnn_infer","rrpn_micro","retinanet_100k","dcn_r50"):
 PY
 cd /tmp
 for WL in maskrcnn_train dcn_r50 maskrcnn_infer retinanet_100k rrpn_micro; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$WL -o bench -- python $REPO/bench.py --workload $WL --steps 20 --warmup 3 --no-cpu-baseline --no-extra-workloads > $OUT/prof_$WL.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$WL -o bench -- python $REPO/bench.py --full --workload $WL --steps 20 --warmup 3 --no-cpu-baseline --no-extra-workloads > $OUT/prof_$WL.log 2>&1
   cp $(find $OUT/prof_$WL -name "*kernel_stats.csv" | head -1) $OUT/${WL}_kernel_stats.csv 2>/dev/null; rm -rf $OUT/prof_$WL
 done

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp PYTHONPATH=$PWD; REPO=$PWD; TAG=${1:-lib_ab}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; shift
 for REP in 1 2; do for S in "$@"; do
   NAME=${S%%:*}; LIB=${S#*:}
-  D2AMD_LIB_PATH=$REPO/$LIB timeout 600 python bench.py --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
+  D2AMD_LIB_PATH=$REPO/$LIB timeout 600 python bench.py --full --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
   python - <<PY
 import json
 d = json.load(open("$OUT/bench_${NAME}_$REP.json"))

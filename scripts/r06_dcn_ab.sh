@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp PYTHONPATH=$PWD; REPO=$PWD; TAG=${1:-r06_dcn_ab}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; shift
 for REP in 1 2 3; do for S in "$@"; do
   NAME=$(echo $S | cut -d: -f1); ENVS=$(echo $S | cut -s -d: -f2 | tr ',' ' ')
-  env $ENVS D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/libd2amd_prof.so timeout 300 python bench.py --workload dcn_r50 --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
+  env $ENVS D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/libd2amd_prof.so timeout 300 python bench.py --full --workload dcn_r50 --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
   python - <<PY
 import json
 try:

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp PYTHONPATH=$PWD; REPO=$PWD; TAG=${1:-r06_infer_ab}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; shift
 for REP in 1 2 3; do for S in "$@"; do
   NAME=$(echo $S | cut -d: -f1); LIB=$(echo $S | cut -d: -f2)
-  D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/$LIB timeout 300 python bench.py --workload maskrcnn_infer --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
+  D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/$LIB timeout 300 python bench.py --full --workload maskrcnn_infer --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
   python - <<PY
 import json
 try:

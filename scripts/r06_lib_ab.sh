@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp PYTHONPATH=$PWD; REPO=$PWD; TAG=${1:-r06_ab}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; shift
 for REP in 1 2 3; do for S in "$@"; do
   NAME=$(echo $S | cut -d: -f1); LIB=$(echo $S | cut -d: -f2); ENVS=$(echo $S | cut -s -d: -f3 | tr ',' ' ')
-  env $ENVS D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/$LIB timeout 300 python bench.py --no-cpu-baseline --no-extra-workloads > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
+  env $ENVS D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/$LIB timeout 300 python bench.py --full --no-cpu-baseline --no-extra-workloads > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
   python - <<PY
 import json
 try:

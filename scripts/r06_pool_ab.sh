@@ -8,7 +8,7 @@ if [ "$2" != "notest" ]; then
 fi
 line() {  # name, env...
   NAME=$1; shift
-  env "$@" D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/libd2amd_prof.so timeout 300 python bench.py --no-cpu-baseline --no-extra-workloads > $OUT/bench_$NAME.json 2> $OUT/bench_$NAME.err
+  env "$@" D2AMD_LIB_PATH=$REPO/detectron2_amd/lib/libd2amd_prof.so timeout 300 python bench.py --full --no-cpu-baseline --no-extra-workloads > $OUT/bench_$NAME.json 2> $OUT/bench_$NAME.err
   python - <<PY
 import json
 try:

@@ -7,6 +7,6 @@ for P in 0 1; do
 done
 for R in 1 2; do for P in 0 1; do
   if [ $P = 1 ]; then export D2AMD_NMS_ROT_PLAIN=1; else unset D2AMD_NMS_ROT_PLAIN; fi
-  timeout 300 python bench.py --workload rrpn_micro --no-cpu-baseline > $OUT/rrpn_plain${P}_$R.json 2> $OUT/rrpn_plain${P}_$R.err
+  timeout 300 python bench.py --full --workload rrpn_micro --no-cpu-baseline > $OUT/rrpn_plain${P}_$R.json 2> $OUT/rrpn_plain${P}_$R.err
   python -c "import json; d=json.load(open('$OUT/rrpn_plain${P}_$R.json')); print('plain=$P', d['ms_per_step'], {k: v['ms_per_step'] for k, v in d['ops'].items()}, d['roofline']['kernels_ms'], d['config']['nms_kept'])"
 done; done

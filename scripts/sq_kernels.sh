@@ -8,7 +8,7 @@ C="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES SQ_WAIT_INST_LDS"   
 cd /tmp
 for P in A B C; do
   eval CNT=\$$P
-  rm -rf /tmp/sq_$P; timeout 300 rocprofv3 --pmc $CNT --output-format csv -d /tmp/sq_$P -o p -- ${SQ_CMD:-python $REPO/bench.py --workload $WL --no-cpu-baseline --steps 3 --warmup 1} > $OUT/sq_$P.log 2>&1; echo "pass $P rc=$?"
+  rm -rf /tmp/sq_$P; timeout 300 rocprofv3 --pmc $CNT --output-format csv -d /tmp/sq_$P -o p -- ${SQ_CMD:-python $REPO/bench.py --full --workload $WL --no-cpu-baseline --steps 3 --warmup 1} > $OUT/sq_$P.log 2>&1; echo "pass $P rc=$?"
 done
 python - "$OUT" "$@" <<'PY'
 import csv, glob, sys, json, collections

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_topk_large.py tests/test_gpu_dense.p
 for S in "$@"; do
   NAME=${S%%:*}; KV=${S#*:}
   for REP in 1 2; do
-    env $KV timeout 300 python bench.py --workload retinanet_100k --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
+    env $KV timeout 300 python bench.py --full --workload retinanet_100k --no-cpu-baseline > $OUT/bench_${NAME}_$REP.json 2> $OUT/bench_${NAME}_$REP.err
     python -c "import json; d=json.load(open('$OUT/bench_${NAME}_$REP.json')); print('$NAME bench', d['ms_per_step'], d['value'])"
   done
   env $KV timeout 300 python scripts/topk_select_bench.py 2> /dev/null | tee $OUT/select_$NAME.json

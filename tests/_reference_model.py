@@ -406,6 +406,8 @@ def install():
             raise RuntimeError("a `detectron2` package is already imported (%s): the model-level tests need a fresh process "
                                "or must run before tests/_reference_surface.py's Surface" % n)
     sys.meta_path.append(_StubFinder())
+    sys.path_hooks.insert(0, build_ref.pkg_path_hook)  # (the tree's modules are bytecode under build_ref.BYTECODE_SUFFIX)
+    sys.path_importer_cache.pop(_PKG, None)
     sys.path.insert(0, _PKG)
 
     def mod(name, **attrs):

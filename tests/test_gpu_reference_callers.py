@@ -26,7 +26,7 @@ def R():
     if not ref.have_py():
         if os.environ.get("D2AMD_NO_REFERENCE") == "1":
             pytest.skip("D2AMD_NO_REFERENCE=1: reference modules not staged")
-        pytest.fail("oracle/_ref/py/*.pyc missing: run `python -m oracle.build_ref` where /root/reference exists, "
+        pytest.fail("oracle/_ref/py/*.pybc missing: run `python -m oracle.build_ref` where the reference tree exists, "
                     "or set D2AMD_NO_REFERENCE=1 where it legitimately does not")
     return ref.py_callers(d2l)
 

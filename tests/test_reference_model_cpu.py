@@ -2,6 +2,8 @@
 bytecode tree with the stubs of tests/_reference_model.py, its GeneralizedRCNN / RetinaNet build, and the plain-torch
 restatement of torchvision's roi_align that the "reference" backend uses is pinned to the C oracle (itself pinned to the
 reference's known answers, tests/test_oracle_golden.py)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -37,7 +39,10 @@ def test_reference_models_build_from_the_bytecode_tree(rm):
     assert abs(sum(p.numel() for p in model.parameters()) - 44.3e6) < 0.2e6  # Mask R-CNN R50-FPN
     import detectron2.modeling.poolers as poolers
 
-    assert poolers.__file__.endswith(".pyc")  # the reference's own file, not a restatement
+    from oracle import build_ref
+
+    # the reference's own file (its bytecode in the tree build_ref staged), not a restatement
+    assert poolers.__file__ == os.path.join(build_ref.PKG_OUT, "detectron2", "modeling", "poolers" + build_ref.BYTECODE_SUFFIX)
     retina = rm.build_model(rm.retinanet_cfg(), seed=0, device="cpu")
     assert type(retina).__name__ == "RetinaNet"
 
