@@ -40,6 +40,7 @@ SOURCES = {
     "topk.hip": ["-ffp-contract=off"],
     "mask_targets.hip": ["-ffp-contract=off"],
     "mask_head.hip": [],
+    "keypoint_head.hip": ["-ffp-contract=off"],
     "box_head.hip": ["-ffp-contract=off"],
     "polygon_masks.hip": ["-ffp-contract=off"],
     "layout.hip": [],

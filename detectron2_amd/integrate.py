@@ -24,6 +24,8 @@ What is bound, and what it replaces (reference file:line under the Detectron2 tr
   roi_heads/fast_rcnn.py:44-170 fast_rcnn_inference                        -> fast_rcnn_inference_fused
   roi_heads/mask_head.py:33-158 mask_rcnn_loss / mask_rcnn_inference       -> the device-side glue (bit masks cropped for the
       whole batch in one launch)
+  roi_heads/keypoint_head.py:40-132 keypoint_rcnn_loss / keypoint_rcnn_inference -> the fused loss (targets in the kernel, no
+      host read) and the one-launch heatmap decode; rebound in that module only
 
 NOT bound: the samplers (`subsample_labels`, sampling.py:9-54, is defined by torch's RNG; this library's sampler is
 defined by explicit keys -- the same distribution, other draws: a bound sampler changes WHICH rows are sampled, so it is
@@ -120,7 +122,7 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
           only: Optional[Iterable[str]] = None) -> Patched:
     """Bind `detectron2` (default: the imported package) to this library; see the module docstring.  `models`: already
     built models whose ROIPooler instances are converted in place.  `only`: a subset of the fused bindings
-    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "dense"} (default: all of them)."""
+    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "dense"} (default: all of them)."""
     want = lambda k: only is None or k in set(only)
     if detectron2 is None:
         import detectron2  # noqa: F811
@@ -273,6 +275,30 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
     if want("mask_head"):
         _rebind_everywhere(h, pkg, "mask_rcnn_loss", ref_loss, mask_rcnn_loss)
         _rebind_everywhere(h, pkg, "mask_rcnn_inference", mh.mask_rcnn_inference, M.mask_rcnn_inference)
+
+    # ---- keypoint head glue.  Bound in keypoint_head's own namespace ONLY (BaseKeypointRCNNHead.forward,
+    # keypoint_head.py:183-205, looks the two names up there): a package-wide rebind would also replace them in modules
+    # that re-exported the originals for other callers.
+    try:
+        kh = imp("modeling.roi_heads.keypoint_head")
+    except ImportError:  # (a trimmed package without the keypoint head)
+        kh = None
+    if kh is not None and want("keypoint_head"):
+        ref_kp_loss, ref_kp_inference = kh.keypoint_rcnn_loss, kh.keypoint_rcnn_inference
+
+        def keypoint_rcnn_loss(pred_keypoint_logits, instances, normalizer):
+            # CPU tensors, and the batch without instances (whose kpts_num_skipped_batches log stays the reference's)
+            if not pred_keypoint_logits.is_cuda or all(len(i) == 0 for i in instances):
+                return ref_kp_loss(pred_keypoint_logits, instances, normalizer)
+            return M.keypoint_rcnn_loss(pred_keypoint_logits, instances, normalizer)
+
+        def keypoint_rcnn_inference(pred_keypoint_logits, pred_instances):
+            if not pred_keypoint_logits.is_cuda:
+                return ref_kp_inference(pred_keypoint_logits, pred_instances)
+            return M.keypoint_rcnn_inference(pred_keypoint_logits, pred_instances)
+
+        h._set(kh, "keypoint_rcnn_loss", keypoint_rcnn_loss)
+        h._set(kh, "keypoint_rcnn_inference", keypoint_rcnn_inference)
 
     # ---- RetinaNet inference: per-level threshold + top-k + decode and the per-class NMS of the batch in one device
     # pipeline (retinanet.py:257-309, dense_detector.py:186-260: a Python loop over images x levels with a nonzero / topk /

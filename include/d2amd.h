@@ -634,6 +634,37 @@ int d2amd_mask_rcnn_loss_backward_masked(const void* logits, const int64_t* gt_c
                                          const float* grad_loss, const int64_t* rows, int B, int C, int HW, int dtype,
                                          void* grad_logits, void* stream);
 
+/* ---- Keypoint-head glue.  detectron2/structures/keypoints.py:104-235, detectron2/modeling/roi_heads/keypoint_head.py:40-132.
+ * S = side of the square heatmap, 2 <= S <= 64 (EINVAL outside); rois fp32 [., 4] xyxy; nothing here reads the host.
+ * keypoints_to_heatmap (keypoints.py:104-161, Keypoints.to_heatmap): keypoints fp32 [N,K,3] (x, y, visibility) ->
+ *   heatmaps int64 [N,K] = (y_cell * S + x_cell) * valid, valid int64 [N,K]; fp32 in the reference's op order (its
+ *   `S / (x2 - x1)` is reciprocal * S), bit-identical to the CPU ops for boxes of positive extent.  A box of zero / NaN
+ *   extent is an integer cast of inf / nan in the reference (undefined): its rows are marked invalid.
+ * keypoint_rcnn_loss forward (keypoint_head.py:40-96): logits [N,K,S,S] `dtype`; the targets are computed in the kernel;
+ *   loss_out[0] = sum over the valid rows of (logsumexp(row) - row[target]) / normalizer in fp32, normalizer <= 0
+ *   meaning "the number of valid rows" (counted on the device; the reference syncs for it); no valid row -> 0.
+ *   stats_out[0] int64 = number of valid rows, left on the device.  Deterministic (fixed-order reduction).
+ *   workspace: d2amd_keypoint_rcnn_loss_workspace_bytes(N * K) bytes, 8-byte aligned (EINVAL when smaller); it carries
+ *   the valid count, lse and target of every row to the backward.
+ * keypoint_rcnn_loss backward: grad_logits [N,K,S,S] `dtype`, written completely: grad_loss[0] * (softmax(row) -
+ *   onehot(target)) / normalizer in the valid rows, 0 elsewhere (those rows of `logits` are not read).  grad_loss is
+ *   a DEVICE scalar (fp32); `workspace` is the forward's, unchanged; same normalizer.
+ * heatmaps_to_keypoints (keypoints.py:165-235): maps [R,K,S,S] `dtype` -> out fp32 [R,K,4] = (x, y, logit, score) of the
+ *   maximum of the map resized (bicubic, align_corners=False, A = -0.75) to ceil(max(w, 1)) x ceil(max(h, 1)) pixels of
+ *   its ROI -- one launch for all ROIs, the resized map is never stored; extents are clamped to 16,384 px.
+ *   pos (nullable) int32 [R,K] = the argmax's linear index y * W' + x, the lowest among exact fp32 ties.
+ * N == 0 / R == 0 succeed without a launch. */
+int d2amd_keypoints_to_heatmap(const float* keypoints, const float* rois, int N, int K, int S, int64_t* heatmaps,
+                               int64_t* valid, void* stream);
+size_t d2amd_keypoint_rcnn_loss_workspace_bytes(int rows);
+int d2amd_keypoint_rcnn_loss_forward(const void* logits, const float* keypoints, const float* rois, int N, int K, int S,
+                                     int dtype, float normalizer, float* loss_out, int64_t* stats_out, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int d2amd_keypoint_rcnn_loss_backward(const void* logits, const void* workspace, const float* grad_loss, int N, int K,
+                                      int S, int dtype, float normalizer, void* grad_logits, void* stream);
+int d2amd_heatmaps_to_keypoints(const void* maps, const float* rois, int R, int K, int S, int dtype, float* out,
+                                int32_t* pos, void* stream);
+
 /* ---- deformable convolution v1 / v2.  Replaces detectron2._C.deform_conv_forward,
  * deform_conv_backward_input, deform_conv_backward_filter, modulated_deform_conv_forward,
  * modulated_deform_conv_backward (vision.cpp:85-102; csrc/deformable/deform_conv.h:116-375).
