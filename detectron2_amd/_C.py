@@ -165,6 +165,13 @@ _SIGNATURES = {
     "d2amd_keypoint_rcnn_loss_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_keypoint_rcnn_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "d2amd_heatmaps_to_keypoints": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "d2amd_dense_loss_workspace_bytes": (_sz, [_i, ctypes.POINTER(_i), _i]),
+    "d2amd_dense_loss_forward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _i,
+                                      ctypes.POINTER(_i), _i, _i, _i, _i, _f, _f, _i, _f, ctypes.POINTER(_f), _f, _vp, _vp,
+                                      _vp, _vp, _sz, _vp]),
+    "d2amd_dense_loss_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
+                                       _i, ctypes.POINTER(_i), _i, _i, _i, _i, _f, _f, _i, _f, ctypes.POINTER(_f), _f,
+                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "d2amd_deform_conv_workspace_bytes": (_sz, [ctypes.POINTER(DcnParams), _i]),
     "d2amd_deform_conv_forward": (_i, [ctypes.POINTER(DcnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_deform_conv_backward": (_i, [ctypes.POINTER(DcnParams)] + [_vp] * 11 + [_sz, _vp]),

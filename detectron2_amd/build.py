@@ -41,6 +41,7 @@ SOURCES = {
     "mask_targets.hip": ["-ffp-contract=off"],
     "mask_head.hip": [],
     "keypoint_head.hip": ["-ffp-contract=off"],
+    "dense_loss.hip": [],
     "box_head.hip": ["-ffp-contract=off"],
     "polygon_masks.hip": ["-ffp-contract=off"],
     "layout.hip": [],

@@ -26,6 +26,9 @@ What is bound, and what it replaces (reference file:line under the Detectron2 tr
       whole batch in one launch)
   roi_heads/keypoint_head.py:40-132 keypoint_rcnn_loss / keypoint_rcnn_inference -> the fused loss (targets in the kernel, no
       host read) and the one-launch heatmap decode; rebound in that module only
+  meta_arch/retinanet.py:160-210 RetinaNet.losses, proposal_generator/rpn.py:366-429 RPN.losses -> the fused dense-anchor
+      losses (one forward and one backward launch for all images and levels, no host read; smooth_l1 / giou, 4-column
+      boxes, device tensors -- anything else stays the reference's method)
 
 NOT bound: the samplers (`subsample_labels`, sampling.py:9-54, is defined by torch's RNG; this library's sampler is
 defined by explicit keys -- the same distribution, other draws: a bound sampler changes WHICH rows are sampled, so it is
@@ -122,7 +125,7 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
           only: Optional[Iterable[str]] = None) -> Patched:
     """Bind `detectron2` (default: the imported package) to this library; see the module docstring.  `models`: already
     built models whose ROIPooler instances are converted in place.  `only`: a subset of the fused bindings
-    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "dense"} (default: all of them)."""
+    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "dense", "dense_loss"} (default: all of them)."""
     want = lambda k: only is None or k in set(only)
     if detectron2 is None:
         import detectron2  # noqa: F811
@@ -330,6 +333,49 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
             return out
 
         h._set(rn.RetinaNet, "forward_inference", forward_inference)
+
+    # ---- dense-anchor training losses: RPN.losses and RetinaNet.losses
+    def _fused_loss_ok(self, anchors, logits):
+        return (type(self.box2box_transform).__name__ == "Box2BoxTransform" and self.box_reg_loss_type in ("smooth_l1", "giou")
+                and len(anchors) > 0 and anchors[0].tensor.shape[-1] == 4 and len(logits) > 0 and logits[0].is_cuda)
+
+    if want("dense_loss"):
+        ref_rpn_losses = rpn.RPN.losses
+
+        def rpn_losses(self, anchors, pred_objectness_logits, gt_labels, pred_anchor_deltas, gt_boxes):
+            """RPN.losses on the fused kernels.  The event-storage scalars rpn/num_pos_anchors and rpn/num_neg_anchors are
+            NOT logged: `put_scalar` takes a host float, and the counts stay on the device here."""
+            if not _fused_loss_ok(self, anchors, pred_objectness_logits):
+                return ref_rpn_losses(self, anchors, pred_objectness_logits, gt_labels, pred_anchor_deltas, gt_boxes)
+            tr = self.box2box_transform
+            return M.rpn_losses([a.tensor for a in anchors], pred_objectness_logits, gt_labels, pred_anchor_deltas, gt_boxes,
+                                batch_size_per_image=self.batch_size_per_image, box_reg_loss_type=self.box_reg_loss_type,
+                                smooth_l1_beta=self.smooth_l1_beta, box2box_weights=tuple(tr.weights),
+                                loss_weight=self.loss_weight, scale_clamp=tr.scale_clamp)
+
+        h._set(rpn.RPN, "losses", rpn_losses)
+    if rn is not None and want("dense_loss"):
+        ref_retinanet_losses = rn.RetinaNet.losses
+
+        def retinanet_losses(self, anchors, pred_logits, gt_labels, pred_anchor_deltas, gt_boxes):
+            """RetinaNet.losses on the fused kernels.  The EMA of the foreground count lives in a 1-element device tensor
+            (`_d2amd_loss_normalizer`, started from `loss_normalizer` or 100) and the event-storage scalar
+            num_pos_anchors is NOT logged: both would need the count on the host."""
+            if not _fused_loss_ok(self, anchors, pred_logits):
+                return ref_retinanet_losses(self, anchors, pred_logits, gt_labels, pred_anchor_deltas, gt_boxes)
+            tr = self.box2box_transform
+            cls, box, stats = M.dense_anchor_losses(
+                [a.tensor for a in anchors], pred_logits, pred_anchor_deltas, gt_labels, gt_boxes, label_mode="class",
+                alpha=self.focal_loss_alpha, gamma=self.focal_loss_gamma, box_reg_loss_type=self.box_reg_loss_type,
+                smooth_l1_beta=self.smooth_l1_beta, weights=tuple(tr.weights), scale_clamp=tr.scale_clamp)
+            state = self.__dict__.get("_d2amd_loss_normalizer")
+            if state is None or state.device != cls.device:
+                state = torch.full((1,), float(getattr(self, "loss_normalizer", 100)), device=cls.device)
+                self.__dict__["_d2amd_loss_normalizer"] = state
+            normalizer = M.ema_normalizer_(state, stats).reshape(())
+            return {"loss_cls": cls / normalizer, "loss_box_reg": box / normalizer}
+
+        h._set(rn.RetinaNet, "losses", retinanet_losses)
 
     if samplers:
         smp = imp("modeling.sampling")

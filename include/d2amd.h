@@ -665,6 +665,45 @@ int d2amd_keypoint_rcnn_loss_backward(const void* logits, const void* workspace,
 int d2amd_heatmaps_to_keypoints(const void* maps, const float* rois, int R, int K, int S, int dtype, float* out,
                                 int32_t* pos, void* stream);
 
+/* ---- Dense-anchor training losses (RetinaNet focal, RPN objectness BCE) + their box regression, all images and levels
+ * in ONE forward and ONE backward launch.  Replaces meta_arch/retinanet.py:160-210 (RetinaNet.losses),
+ * proposal_generator/rpn.py:366-429 (RPN.losses) and box_regression.py:310-369 (_dense_box_regression_loss): no cat of the
+ * levels, no boolean index, no one-hot, no host read of the foreground count.
+ *   logits[l] [N, A_l, K] and deltas[l] [N, A_l, 4] contiguous, `dtype` (device pointers in host arrays; fp32 compute);
+ *   anchors[l] fp32 [A_l, 4] xyxy; level_anchors (host) [L] = A_l, L <= 8; gt_labels int64 [N, R], gt_boxes fp32 [N, R, 4],
+ *   R = sum A_l, levels in order (the outputs of label_anchors / label_and_sample_anchors, stacked).
+ *   label_mode CLASS: -1 ignore, K background, c < K foreground of class c;  OBJECTNESS (K == 1): -1 ignore, 0
+ *   background, 1 foreground; any other value is ignored.
+ *   classification, per element x with target t, p = sigmoid(x): ce (1 - p_t)^gamma, times alpha_t when alpha >= 0
+ *   (alpha < 0: no weighting, fvcore's convention); gamma == 0 is plain BCE-with-logits; gamma >= 0.
+ *   box term on the foreground rows: box_loss SMOOTH_L1 (|pred delta - get_deltas(anchor, gt)| with `weights`; beta < 1e-5
+ *   is L1) or GIOU (fvcore giou_loss, eps 1e-7, of apply_deltas(delta, anchor) clamped at scale_clamp against gt); any
+ *   other box_loss / label_mode: D2AMD_EUNSUPPORTED, nothing launched.
+ * forward: loss_cls_sum, loss_box_sum fp32 scalars (SUMS: the caller divides), stats int64[2] = (#foreground rows,
+ *   #valid rows), all on the device.  workspace: d2amd_dense_loss_workspace_bytes(N, level_anchors, L) bytes, 8-byte
+ *   aligned, one record per tile of 256 anchors; the records are added in fp64 in a fixed order: two runs are bit-identical.
+ *   No tile (N == 0, L == 0 or empty levels) writes zeros.
+ * backward: grad_cls, grad_box are DEVICE fp32 scalars (the upstream gradients of the two sums); grad_logits[l] /
+ *   grad_deltas[l] (`dtype`, shapes of the inputs, grad_deltas[l] aligned to a row of four) are written completely, zeros
+ *   for ignored rows and for the deltas of rows that are not foreground; the gradient is recomputed from the logits
+ *   (the forward saves nothing per element), a delta clamped at scale_clamp gets 0. */
+#define D2AMD_DENSE_LABELS_CLASS 0
+#define D2AMD_DENSE_LABELS_OBJECTNESS 1
+#define D2AMD_BOX_LOSS_SMOOTH_L1 0
+#define D2AMD_BOX_LOSS_GIOU 1
+size_t d2amd_dense_loss_workspace_bytes(int N, const int* level_anchors, int L);
+int d2amd_dense_loss_forward(const void* const* logits, const void* const* deltas, const float* const* anchors,
+                             const int64_t* gt_labels, const float* gt_boxes, int N, const int* level_anchors, int L,
+                             int K, int dtype, int label_mode, float alpha, float gamma, int box_loss,
+                             float smooth_l1_beta, const float* weights, float scale_clamp, float* loss_cls_sum,
+                             float* loss_box_sum, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+int d2amd_dense_loss_backward(const void* const* logits, const void* const* deltas, const float* const* anchors,
+                              const int64_t* gt_labels, const float* gt_boxes, const float* grad_cls,
+                              const float* grad_box, int N, const int* level_anchors, int L, int K, int dtype,
+                              int label_mode, float alpha, float gamma, int box_loss, float smooth_l1_beta,
+                              const float* weights, float scale_clamp, void* const* grad_logits,
+                              void* const* grad_deltas, void* stream);
+
 /* ---- deformable convolution v1 / v2.  Replaces detectron2._C.deform_conv_forward,
  * deform_conv_backward_input, deform_conv_backward_filter, modulated_deform_conv_forward,
  * modulated_deform_conv_backward (vision.cpp:85-102; csrc/deformable/deform_conv.h:116-375).
