@@ -172,7 +172,12 @@ _SIGNATURES = {
     "d2amd_dense_loss_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
                                        _i, ctypes.POINTER(_i), _i, _i, _i, _i, _f, _f, _i, _f, ctypes.POINTER(_f), _f,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
-    "d2amd_deform_conv_workspace_bytes": (_sz, [ctypes.POINTER(DcnParams), _i]),
+    "d2amd_fast_rcnn_loss_workspace_bytes": (_sz, [_i]),
+    "d2amd_fast_rcnn_loss_forward": (_i, [_vp] * 7 + [_i] * 8 + [_vp, _i, _f, ctypes.POINTER(_f), _f, _vp, _vp, _vp, _sz,
+                                          _vp]),
+    "d2amd_fast_rcnn_loss_backward": (_i, [_vp] * 9 + [_i] * 8 + [_vp, _i, _f, ctypes.POINTER(_f), _f, _vp, _sz, _vp, _vp,
+                                           _vp]),
+    "d2amd_deform_conv_workspace_bytes":(_sz, [ctypes.POINTER(DcnParams), _i]),
     "d2amd_deform_conv_forward": (_i, [ctypes.POINTER(DcnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_deform_conv_backward": (_i, [ctypes.POINTER(DcnParams)] + [_vp] * 11 + [_sz, _vp]),
     "d2amd_deform_conv_columns_bytes": (_sz, [ctypes.POINTER(DcnParams)]),

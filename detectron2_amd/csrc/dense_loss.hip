@@ -32,6 +32,7 @@
 // Roofline (RetinaNet, 2 x 800 x 1344, K = 80, bf16: 32.3 M logits): forward reads 64.5 MB, backward reads 64.5 MB and
 // writes 64.5 MB; three quarter-rate transcendentals per element put the VALU time in the same range.
 #include "common.h"
+#include "loss_common.h"
 
 namespace d2amd {
 
@@ -110,40 +111,6 @@ __device__ __forceinline__ int2 dl_stage_labels(const int64_t* __restrict__ gt_l
   return make_int2(s_cnt[0], s_cnt[1]);
 }
 
-// ---- 16-byte vectors of T <-> fp32 ------------------------------------------------------------------------------
-template <typename T> struct dl_vec { static constexpr int N = 16 / (int)sizeof(T); };
-
-__device__ __forceinline__ void dl_load16(const float* p, float (&o)[4]) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-}
-template <typename T> __device__ __forceinline__ void dl_load16(const T* p, float (&o)[8]) {
-  const uint4 v = *reinterpret_cast<const uint4*>(p);
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    o[2 * q] = to_f32(T{(uint16_t)(w[q] & 0xffffu)});
-    o[2 * q + 1] = to_f32(T{(uint16_t)(w[q] >> 16)});
-  }
-}
-__device__ __forceinline__ void dl_store16(float* p, const float (&i)[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(i[0], i[1], i[2], i[3]);
-}
-template <typename T> __device__ __forceinline__ void dl_store16(T* p, const float (&i)[8]) {
-  uint32_t w[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    w[q] = (uint32_t)from_f32<T>(i[2 * q]).v | ((uint32_t)from_f32<T>(i[2 * q + 1]).v << 16);
-  *reinterpret_cast<uint4*>(p) = uint4{w[0], w[1], w[2], w[3]};
-}
-
-// elements in front of the first 16-byte boundary at or behind p (all of them when `vec` is off)
-template <typename T> __device__ __forceinline__ int dl_head(const T* p, int count, bool vec) {
-  if (!vec) return count;
-  const int h = (int)(((16u - (uint32_t)((uintptr_t)p & 15u)) & 15u) / (uint32_t)sizeof(T));
-  return min(h, count);
-}
-
 // ---- focal / BCE term (fvcore sigmoid_focal_loss, F.binary_cross_entropy_with_logits) ---------------------------
 // GM: 0 gamma == 0, 2 gamma == 2, 1 any other gamma > 0
 __device__ __forceinline__ float dl_alpha_t(bool t, float alpha) { return alpha >= 0.f ? (t ? alpha : 1.f - alpha) : 1.f; }
@@ -184,68 +151,6 @@ template <int GM> __device__ __forceinline__ float dl_focal_grad(float x, int co
   return code < 0 ? 0.f : v;
 }
 
-// ---- box term of one foreground anchor (box_regression.py:43-116, fvcore smooth_l1_loss / giou_loss) -----------
-// torch's rule for max / min of equal arguments: the gradient is shared
-__device__ __forceinline__ float dl_sel_gt(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
-
-// -> loss; g[0..3] = d loss / d delta
-__device__ __forceinline__ float dl_box_term(const float (&an)[4], const float (&gt)[4], const float (&d)[4],
-                                             const DlParams& p, float (&g)[4]) {
-  const float w = an[2] - an[0], h = an[3] - an[1];
-  const float cx = an[0] + 0.5f * w, cy = an[1] + 0.5f * h;
-  if (!p.giou) {
-    const float tw = gt[2] - gt[0], th = gt[3] - gt[1];
-    const float tcx = gt[0] + 0.5f * tw, tcy = gt[1] + 0.5f * th;
-    const float tgt[4] = {p.wx * (tcx - cx) / w, p.wy * (tcy - cy) / h, p.ww * logf(tw / w), p.wh * logf(th / h)};
-    float loss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const float r = d[i] - tgt[i], n = fabsf(r);
-      const float sgn = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
-      if (p.beta < 1e-5f || !(n < p.beta)) {
-        loss += p.beta < 1e-5f ? n : n - 0.5f * p.beta;
-        g[i] = sgn;
-      } else {
-        loss += 0.5f * n * n / p.beta;
-        g[i] = r / p.beta;
-      }
-    }
-    return loss;
-  }
-  // apply_deltas, then GIoU with eps = 1e-7
-  const float dx = d[0] / p.wx, dy = d[1] / p.wy;
-  const float dw0 = d[2] / p.ww, dh0 = d[3] / p.wh;
-  const float dw = fminf(dw0, p.scale_clamp), dh = fminf(dh0, p.scale_clamp);
-  const float pcx = dx * w + cx, pcy = dy * h + cy;
-  const float pw = expf(dw) * w, ph = expf(dh) * h;
-  const float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
-  const float X1 = gt[0], Y1 = gt[1], X2 = gt[2], Y2 = gt[3];
-  constexpr float eps = 1e-7f;
-  const float iw = fminf(x2, X2) - fmaxf(x1, X1), ih = fminf(y2, Y2) - fmaxf(y1, Y1);
-  const bool hit = iw > 0.f && ih > 0.f;
-  const float I = hit ? iw * ih : 0.f;
-  const float bw = x2 - x1, bh = y2 - y1;
-  const float U = bw * bh + (X2 - X1) * (Y2 - Y1) - I;
-  const float cw = fmaxf(x2, X2) - fminf(x1, X1), ch = fmaxf(y2, Y2) - fminf(y1, Y1);
-  const float C = cw * ch;
-  const float iu = 1.f / (U + eps), ic = 1.f / (C + eps);
-  const float loss = 1.f - I * iu + (C - U) * ic;
-  // loss(I, U, C) with U = area_pred + area_gt - I
-  const float gU = I * iu * iu - ic;
-  const float gI = -iu - gU;
-  const float gC = (U + eps) * ic * ic;
-  const float hI = hit ? gI : 0.f;
-  const float gx1 = -gU * bh - hI * ih * dl_sel_gt(x1, X1) - gC * ch * dl_sel_gt(X1, x1);
-  const float gx2 = gU * bh + hI * ih * dl_sel_gt(X2, x2) + gC * ch * dl_sel_gt(x2, X2);
-  const float gy1 = -gU * bw - hI * iw * dl_sel_gt(y1, Y1) - gC * cw * dl_sel_gt(Y1, y1);
-  const float gy2 = gU * bw + hI * iw * dl_sel_gt(Y2, y2) + gC * cw * dl_sel_gt(y2, Y2);
-  g[0] = (gx1 + gx2) * w / p.wx;
-  g[1] = (gy1 + gy2) * h / p.wy;
-  g[2] = dw0 > p.scale_clamp ? 0.f : 0.5f * (gx2 - gx1) * pw / p.ww;  // a clamped delta has no gradient
-  g[3] = dh0 > p.scale_clamp ? 0.f : 0.5f * (gy2 - gy1) * ph / p.wh;
-  return loss;
-}
-
 // anchor `a` of the tile (foreground) -> its box loss and delta gradient
 template <typename T>
 __device__ __forceinline__ float dl_box_row(const DlTile& t, const float* __restrict__ gt_boxes, const DlParams& p, int a,
@@ -256,12 +161,6 @@ __device__ __forceinline__ float dl_box_row(const DlTile& t, const float* __rest
   const float av[4] = {an[0], an[1], an[2], an[3]}, gv[4] = {gb[0], gb[1], gb[2], gb[3]};
   const float dv[4] = {to_f32(dr[0]), to_f32(dr[1]), to_f32(dr[2]), to_f32(dr[3])};
   return dl_box_term(av, gv, dv, p, g);
-}
-
-__device__ __forceinline__ float dl_wave_sum(float v) {  // butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------

@@ -29,6 +29,8 @@ What is bound, and what it replaces (reference file:line under the Detectron2 tr
   meta_arch/retinanet.py:160-210 RetinaNet.losses, proposal_generator/rpn.py:366-429 RPN.losses -> the fused dense-anchor
       losses (one forward and one backward launch for all images and levels, no host read; smooth_l1 / giou, 4-column
       boxes, device tensors -- anything else stays the reference's method)
+  roi_heads/fast_rcnn.py:307-352 FastRCNNOutputLayers.losses               -> the fused box-head loss (`fast_rcnn_losses`: no
+      argmax / nonzero / gather, no host read), ONLY when `only` names "box_loss": it is not part of the default set
 
 NOT bound: the samplers (`subsample_labels`, sampling.py:9-54, is defined by torch's RNG; this library's sampler is
 defined by explicit keys -- the same distribution, other draws: a bound sampler changes WHICH rows are sampled, so it is
@@ -125,7 +127,8 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
           only: Optional[Iterable[str]] = None) -> Patched:
     """Bind `detectron2` (default: the imported package) to this library; see the module docstring.  `models`: already
     built models whose ROIPooler instances are converted in place.  `only`: a subset of the fused bindings
-    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "dense", "dense_loss"} (default: all of them)."""
+    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "dense", "dense_loss"} (default: all of them), and "box_loss", which is bound
+    only when named here."""
     want = lambda k: only is None or k in set(only)
     if detectron2 is None:
         import detectron2  # noqa: F811
@@ -376,6 +379,41 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
             return {"loss_cls": cls / normalizer, "loss_box_reg": box / normalizer}
 
         h._set(rn.RetinaNet, "losses", retinanet_losses)
+
+    # ---- box head training loss: FastRCNNOutputLayers.losses.  Bound only when NAMED in `only`.
+    if only is not None and "box_loss" in set(only):
+        ref_box_losses = fr.FastRCNNOutputLayers.losses
+
+        def box_losses(self, predictions, proposals):
+            """FastRCNNOutputLayers.losses on the fused kernels.  The event-storage scalars fast_rcnn/cls_accuracy,
+            fast_rcnn/fg_cls_accuracy and fast_rcnn/false_negative are NOT logged: `put_scalar` takes host floats, and
+            the five counts they are made of stay on the device, in `self._d2amd_box_loss_stats` (int64 [5]: rows,
+            foreground rows, accurate, accurate foreground, foreground predicted as background)."""
+            scores, proposal_deltas = predictions
+            if (type(self.box2box_transform).__name__ != "Box2BoxTransform" or not scores.is_cuda or len(proposals) == 0
+                    or self.box_reg_loss_type not in ("smooth_l1", "giou")
+                    or proposals[0].proposal_boxes.tensor.shape[-1] != 4):
+                return ref_box_losses(self, predictions, proposals)
+            gt_classes = torch.cat([p.gt_classes for p in proposals], dim=0)
+            proposal_boxes = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
+            gt_boxes = torch.cat([(p.gt_boxes if p.has("gt_boxes") else p.proposal_boxes).tensor for p in proposals], dim=0)
+            class_weight = None
+            if self.use_sigmoid_ce and getattr(self, "use_fed_loss", False):
+                k = scores.shape[1] - 1
+                keep = self.get_fed_loss_classes(gt_classes, num_fed_loss_classes=self.fed_loss_num_classes, num_classes=k,
+                                                 weight=self.fed_loss_cls_weights)
+                mask = keep.new_zeros(k + 1)
+                mask[keep] = 1
+                class_weight = mask[:k].float()
+            tr = self.box2box_transform
+            losses, stats = M.fast_rcnn_losses_with_stats(
+                scores, proposal_deltas, gt_classes, proposal_boxes, gt_boxes, box_reg_loss_type=self.box_reg_loss_type,
+                smooth_l1_beta=self.smooth_l1_beta, box2box_weights=tuple(tr.weights), scale_clamp=tr.scale_clamp,
+                loss_weight=self.loss_weight, use_sigmoid_ce=self.use_sigmoid_ce, class_weight=class_weight)
+            self.__dict__["_d2amd_box_loss_stats"] = stats
+            return losses
+
+        h._set(fr.FastRCNNOutputLayers, "losses", box_losses)
 
     if samplers:
         smp = imp("modeling.sampling")

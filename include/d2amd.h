@@ -704,6 +704,51 @@ int d2amd_dense_loss_backward(const void* const* logits, const void* const* delt
                               const float* weights, float scale_clamp, void* const* grad_logits,
                               void* const* grad_deltas, void* stream);
 
+/* ---- Box-head training loss (Fast R-CNN classification + box regression), fused.  Replaces
+ * modeling/roi_heads/fast_rcnn.py:307-352 (FastRCNNOutputLayers.losses) with :88-115 (_log_classification_stats),
+ * :386-422 (sigmoid_cross_entropy_loss) and :424-463 (box_reg_loss): no argmax / nonzero / gather launches, no host read.
+ *   scores [R, K+1] `dtype` (last column: background), deltas [R, delta_cols] `dtype` with delta_cols 4 (class-agnostic)
+ *   or 4 K; gt_classes int64 [R]; proposal_boxes fp32 [R, 4] xyxy.  The matched ground-truth box of row r is
+ *   gt_boxes[r] (gt_index NULL: gt_boxes is fp32 [R, 4]) or gt_boxes[gt_offsets[r / rows_per_image] + gt_index[r]]
+ *   (the sampler's form: gt_boxes is a stacked table fp32 [gt_rows, 4], gt_index int64 [R], gt_offsets int64
+ *   [num_images], num_images * rows_per_image >= R; the index is clamped to the table).
+ *   A row COUNTS if its class is in [0, K]; [0, K) is foreground, K background; every other class (the sampler's -1) is
+ *   padding: no loss, no statistic, zero gradient.  Both losses are divided by the number of rows that count, counted on
+ *   the device (the reference's gt_classes.numel() when nothing is padded); no such row -> both 0.
+ *   cls_loss SOFTMAX: cross-entropy over the K+1 columns;  SIGMOID: BCE-with-logits over the first K columns against the
+ *   one-hot target (background rows: all zero), every row multiplied by class_weight fp32 [K] when not NULL (the
+ *   federated-loss class mask).  box_loss / smooth_l1_beta / weights[4] / scale_clamp: as d2amd_dense_loss_forward, on
+ *   the four deltas of the row's own class (or its only four), foreground rows only.
+ *   EINVAL before any launch: a null pointer (R > 0), K < 1, delta_cols not in {4, 4 K}, an unknown dtype / cls_loss /
+ *   box_loss (diou, ciou), a short or misaligned workspace, (K + 1) * sizeof(dtype) above 60 KB.
+ * forward: loss_out fp32 [2] = (loss_cls, loss_box_reg), before any loss weight; stats_out int64 [5] = (rows that count,
+ *   foreground rows, argmax == class, foreground with argmax == class, foreground with argmax == K), argmax over the
+ *   K+1 columns with the lowest index among exact ties; all left on the device.  workspace:
+ *   d2amd_fast_rcnn_loss_workspace_bytes(R) bytes, 8-byte aligned: the row count, each row's (max, sum exp) and one
+ *   record per workgroup; the records are added in fp64 in a fixed order: two runs are bit-identical.
+ * backward: grad_cls, grad_box are DEVICE fp32 scalars (upstream gradients of the two losses); `workspace` is the
+ *   forward's, unchanged.  grad_scores [R, K+1] and grad_deltas [R, delta_cols] (`dtype`) are written completely:
+ *   (softmax - onehot) / rows or (sigmoid - target) * class_weight / rows (background column 0), zeros in padding rows
+ *   (whose logits are not used), and zeros in grad_deltas but the four entries of a foreground row's class.
+ * R == 0 succeeds and launches nothing (outputs untouched). */
+#define D2AMD_CLS_LOSS_SOFTMAX 0
+#define D2AMD_CLS_LOSS_SIGMOID 1
+size_t d2amd_fast_rcnn_loss_workspace_bytes(int R);
+int d2amd_fast_rcnn_loss_forward(const void* scores, const void* deltas, const int64_t* gt_classes,
+                                 const float* proposal_boxes, const float* gt_boxes, const int64_t* gt_index,
+                                 const int64_t* gt_offsets, int R, int K, int delta_cols, int rows_per_image,
+                                 int num_images, int gt_rows, int dtype, int cls_loss, const float* class_weight,
+                                 int box_loss, float smooth_l1_beta, const float* weights, float scale_clamp,
+                                 float* loss_out, int64_t* stats_out, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int d2amd_fast_rcnn_loss_backward(const void* scores, const void* deltas, const int64_t* gt_classes,
+                                  const float* proposal_boxes, const float* gt_boxes, const int64_t* gt_index,
+                                  const int64_t* gt_offsets, const float* grad_cls, const float* grad_box, int R, int K,
+                                  int delta_cols, int rows_per_image, int num_images, int gt_rows, int dtype,
+                                  int cls_loss, const float* class_weight, int box_loss, float smooth_l1_beta,
+                                  const float* weights, float scale_clamp, const void* workspace,
+                                  size_t workspace_bytes, void* grad_scores, void* grad_deltas, void* stream);
+
 /* ---- deformable convolution v1 / v2.  Replaces detectron2._C.deform_conv_forward,
  * deform_conv_backward_input, deform_conv_backward_filter, modulated_deform_conv_forward,
  * modulated_deform_conv_backward (vision.cpp:85-102; csrc/deformable/deform_conv.h:116-375).
