@@ -12,7 +12,9 @@
 //      gathers -- 25 us for the 7-bit class sort of 100,000 boxes against 49 us of rocPRIM's radix sort, which
 //      this file no longer uses.  Callers whose input consists of pre-sorted RUNS (the per-level top-k
 //      lists of the RPN / dense detectors: d2amd_nms_runs) get the order from a merge instead -- step 1c below;
-//      for the RPN (runs = categories, n <= 12,288) the whole pipeline is 4 launches.
+//      for the RPN (runs = categories, n <= 12,288) the whole pipeline is 4 launches: records, mask, reduction with
+//      the merge running BESIDE it (extra workgroups of the same launch), finalize -- mask and reduction never read
+//      the order, so it is not computed in front of them.
 //   2. wavefront bitmask kernel: one 64-lane wave per 64x64 tile of the (sorted) IoU matrix,
 //        lane = row box, one uint64 word per lane; only tiles on/above the diagonal whose
 //        category ranges overlap are evaluated (pair count = sum_c n_c^2/2, not N^2/2).
@@ -23,6 +25,7 @@
 // Bit-exactness: IoU arithmetic is evaluated exactly as torchvision's CPU nms / the reference's
 // nms_rotated_cpu.cpp (fp32, no FMA contraction, IEEE divide, threshold compare in double).
 #pragma clang fp contract(off)
+#include <cstdlib>
 #include <cstring>
 
 #include "common.h"
@@ -498,6 +501,10 @@ __device__ __forceinline__ void nms_runs_rank_body(const float* __restrict__ box
 // launch, no dependent load of the runs' counts, nothing written to and read back from memory in between
 // (scan 5 us + rank 17 us -> one kernel).  It also zeroes the reduction's accumulators (plain stores: nothing else in
 // this launch touches them) and reports "a run is not in order" through a per-workgroup word.
+// Runs = categories: the same body runs as the extra workgroups of the reduction launch (`side`: nms_reduce_order_kernel),
+// where it writes order[], rankpos, cls_s, the zeroed blk_cnt and the "not in order" words only -- the records and the
+// zeroed accumulators, all that mask and reduction read of step 1, come from nms_runs_records_kernel in front of the mask.
+// As a launch of its own it remains for runs that are not categories and under D2AMD_NMS_ORDER_FIRST.
 // Workgroups of 256 threads (35 of them for 8,819 entries): with 1,024-thread workgroups the kernel ran on 9 CUs and
 // was bound by their VALUs (the 11-step search of 4 other runs is ~1,100 instructions per entry: 22 us); a workgroup
 // walks the n keys twice (count, then place: the second pass re-reads them from cache) instead of holding them.
@@ -516,21 +523,27 @@ __device__ __forceinline__ void nms_runs_order_small_body(
     const float* __restrict__ boxes, const float* __restrict__ scores, int n, const NmsRuns& R,
     int* __restrict__ order, int* __restrict__ rankpos, uint32_t* __restrict__ cls_s, float* __restrict__ boxes_s,
     uint32_t* __restrict__ zero, int zero_words, int* __restrict__ blk_zero, int blk_words,
-    int* __restrict__ blk_flag, int records) {
-  __shared__ uint32_t samp[RANK_MAX_N], s_raw[RANK_MAX_N];  // live keys compacted / all keys in array order
+    int* __restrict__ blk_flag, int records, uint32_t* __restrict__ samp, uint32_t* __restrict__ s_raw, int blk,
+    int nblk, bool side) {
+  // samp / s_raw [RANK_MAX_N] each (LDS, the caller's): live keys compacted / all keys in array order.
+  // blk of nblk: this workgroup's ORDER_THREADS entries.  side: the workgroup runs beside the reduction
+  // (nms_reduce_order_kernel) -- the records and the zeroed accumulators were written in front of the mask, only
+  // order[], rankpos, cls_s, blk_zero and blk_flag are left to write.
   __shared__ int cell[ORDER_ROWS * ORDER_WAVES + 1];
   __shared__ int s_sbase[NMS_MAX_RUNS + 1], s_off[NMS_MAX_RUNS + 1];
   __shared__ int s_bad;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (blockIdx.x * ORDER_THREADS >= n) return;  // uniform (batched launch: the grid is sized for the largest image)
-  for (int q = blockIdx.x * ORDER_THREADS + tid; q < zero_words; q += gridDim.x * ORDER_THREADS) zero[q] = 0u;
-  if (blockIdx.x == 0 && tid < blk_words) blk_zero[tid] = 0;
+  if (blk * ORDER_THREADS >= n) return;  // uniform (batched launch: the grid is sized for the largest image)
+  if (!side)
+    for (int q = blk * ORDER_THREADS + tid; q < zero_words; q += nblk * ORDER_THREADS) zero[q] = 0u;
+  if (blk == 0 && tid < blk_words) blk_zero[tid] = 0;
   // my own entry's box: requested first, it arrives while the keys are compacted
-  const int i = blockIdx.x * ORDER_THREADS + tid;
+  const int i = blk * ORDER_THREADS + tid;
   const long bi = min(i, n - 1);
   float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float b5 = 0.f;
-  if (BW == 4) {
+  if (side) {
+  } else if (BW == 4) {
     b4 = *reinterpret_cast<const float4*>(boxes + bi * 4);
   } else {
     const float* bp = boxes + bi * BW;
@@ -593,7 +606,7 @@ __device__ __forceinline__ void nms_runs_order_small_body(
     const unsigned long long bal = __ballot(live);
     const int g = cell[k * ORDER_WAVES + wid] + __builtin_popcountll(bal & ((1ull << lane) - 1ull));  // live before j
     if (live) samp[g] = kk;
-    if (k == (int)blockIdx.x) { g_mine = g; keyv = kk; }
+    if (k == blk) { g_mine = g; keyv = kk; }
   }
   // start of run q in the flat compaction = live entries before off[q]: wave q % 4 recounts the 64 entries around
   // off[q] (comparing every entry of every row with every run start was 6 us)
@@ -664,7 +677,8 @@ __device__ __forceinline__ void nms_runs_order_small_body(
       const int p = to_rank ? rank : i;
       const uint32_t cls = to_rank ? 0u : (uint32_t)r;
       float* d = boxes_s + (long)p * BOX_REC;
-      if (BW == 4) {
+      if (side) {
+      } else if (BW == 4) {
         const float area = (b4.z - b4.x) * (b4.w - b4.y);
         const bool fin = (fabsf(b4.x) < INFINITY) && (fabsf(b4.y) < INFINITY) && (fabsf(b4.z) < INFINITY) &&
                          (fabsf(b4.w) < INFINITY);
@@ -678,7 +692,25 @@ __device__ __forceinline__ void nms_runs_order_small_body(
     }
   }
   __syncthreads();
-  if (tid == 0) blk_flag[blockIdx.x] = s_bad ? 4 : 0;
+  if (tid == 0) blk_flag[blk] = s_bad ? 4 : 0;
+}
+
+// Runs = categories, n <= RANK_MAX_N: what the mask and the reduction need of step 1 does not depend on the scores --
+// the class-major position of a box is its array position and its category is its run.  This streaming kernel writes
+// the box records and zeroes the reduction's accumulators (one load round trip, no LDS, no search); the score order
+// itself is first read by the finalize kernel and is merged beside the reduction (nms_reduce_order_kernel).
+template <int BW>
+__device__ __forceinline__ void nms_runs_records_body(const float* __restrict__ boxes, int n, const NmsRuns& R,
+                                                      float* __restrict__ boxes_s, uint32_t* __restrict__ zero,
+                                                      int zero_words) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  for (int q = i; q < zero_words; q += gridDim.x * blockDim.x) zero[q] = 0u;  // (the grid is never empty)
+  if (i >= n) return;
+  int r = 0;
+#pragma unroll
+  for (int q = 1; q < NMS_MAX_RUNS; q++)
+    if (i >= R.off[q] && q < R.n_runs) r = q;  // (constant indices: see nms_reduce_body)
+  store_box_record<BW>(boxes_s, i, boxes + (long)i * BW, (uint32_t)r);
 }
 
 // order[] entries as indices: a run that was announced as sorted but is not (flag 4) leaves ranks that are no
@@ -1345,6 +1377,11 @@ constexpr int RED_THREADS = 64 * (1 + RED_GROUPS);
 constexpr int RED_SPLIT = 2;         // a block's 64 rows are pushed as 2 units of 32 rows: 64 VGPRs of rows per pusher
 constexpr int RED_PUSH_ROWS = 64 / RED_SPLIT;  // (64-row units needed 128 VGPRs and spilled, which serialised the row loads)
 constexpr int RED_WIN = 64;         // blocks of (DT, word 1) staged in LDS at a time (2 x 32 KiB)
+constexpr int RED_WIN_WORDS = 3 * RED_WIN * 64;  // DT, word 1, word 2: 96 KiB, one buffer owned by the kernel
+// (the order workgroups of nms_reduce_order_kernel put their two key arrays into the same buffer: a workgroup has one
+// role, and the two roles' arrays together do not fit the CU's 160 KiB)
+static_assert(RED_WIN_WORDS * 8 >= 2 * RANK_MAX_N * 4, "the order body's keys must fit the reduction's windows");
+static_assert(RED_THREADS == ORDER_THREADS, "nms_reduce_order_kernel: one workgroup size for both roles");
 
 __device__ __forceinline__ void nms_reduce_body(const u64* __restrict__ mask,
                                                                  const u64* __restrict__ diagT,
@@ -1353,9 +1390,13 @@ __device__ __forceinline__ void nms_reduce_body(const u64* __restrict__ mask,
                                                                  const uint32_t* __restrict__ cls_s, int n, int wcap,
                                                                  int max_per_class, const int* __restrict__ seg_start,
                                                                  const NmsRuns& R, bool runs, int* counters,
-                                                                 u64* keepbits, u64* dbg) {
+                                                                 u64* keepbits, u64* dbg, u64* __restrict__ win,
+                                                                 int seg_stride) {
+  // win [RED_WIN_WORDS] (LDS, the caller's): the staged windows.  seg_stride: workgroups of the launch that reduce.
   extern __shared__ __attribute__((aligned(16))) u64 removed[];  // [wcap]
-  __shared__ u64 dt_s[RED_WIN * 64], wt_s[RED_WIN * 64], wu_s[RED_WIN * 64];
+  u64* const dt_s = win;
+  u64* const wt_s = win + RED_WIN * 64;
+  u64* const wu_s = win + 2 * RED_WIN * 64;
   __shared__ u64 kept_s[RED_WIN];
   __shared__ int flag_s[1 + RED_GROUPS];  // [0] blocks resolved by wave 0; [1 + g] blocks pushed by pusher g
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1365,7 +1406,7 @@ __device__ __forceinline__ void nms_reduce_body(const u64* __restrict__ mask,
   // (the run table is read with constant indices only: a dynamic index -- or a pointer -- into the kernel-argument
   // struct makes the compiler copy the struct to scratch memory: 560 us)
   const int nseg = runs ? R.n_runs : (cls_s ? counters[0] : 1);
-  for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+  for (int seg = blockIdx.x; seg < nseg; seg += seg_stride) {
     if (dbg && seg == 0 && tid == 0) dbg[120] = wall_clock64();
     int s = 0, e = n;
     if (runs) {
@@ -1829,9 +1870,16 @@ __global__ __launch_bounds__(RUNS_SCAN_THREADS) void nms_runs_scan_kernel(const 
 template <int BW>
 __global__ __launch_bounds__(ORDER_THREADS) void nms_runs_order_small_kernel(const NmsBatch B) {
   const NmsImg& I = B.img[blockIdx.z];
+  __shared__ uint32_t keys_s[2 * RANK_MAX_N];
   nms_runs_order_small_body<BW>(I.boxes, I.scores, I.n, B.runs, I.w.order, I.w.rankpos, I.w.cls_s, I.w.boxes_s,
                                 (uint32_t*)I.w.keepbits, (int)(I.w.zero_bytes / 4), I.w.blk_cnt, 2 * (I.n / 1024 + 2),
-                                I.w.run_cnt + 16, I.idxs ? 0 : 1);
+                                I.w.run_cnt + 16, I.idxs ? 0 : 1, keys_s, keys_s + RANK_MAX_N, (int)blockIdx.x,
+                                (int)gridDim.x, false);
+}
+template <int BW>
+__global__ void nms_runs_records_kernel(const NmsBatch B) {
+  const NmsImg& I = B.img[blockIdx.z];
+  nms_runs_records_body<BW>(I.boxes, I.n, B.runs, I.w.boxes_s, (uint32_t*)I.w.keepbits, (int)(I.w.zero_bytes / 4));
 }
 constexpr int RUNS_RANK_THREADS = 1024;  // every workgroup stages all samples: few, large workgroups
 template <int BW>
@@ -1861,8 +1909,29 @@ __global__ __launch_bounds__(64 * ROTW, ROT_OCC) void nms_mask_rot_wg_kernel(con
 }
 __global__ __launch_bounds__(RED_THREADS) void nms_reduce_kernel(const NmsBatch B) {
   const NmsImg& I = B.img[blockIdx.z];
+  __shared__ u64 win[RED_WIN_WORDS];
   nms_reduce_body(I.w.mask, I.w.diagT, I.w.w1T, I.w.w2T, I.cls_s, I.n, I.wcap, I.mpc, I.w.seg_start,
-                  B.runs, B.runs.are_cls != 0, I.w.counters, I.w.keepbits, blockIdx.z == 0 ? B.dbg : nullptr);
+                  B.runs, B.runs.are_cls != 0, I.w.counters, I.w.keepbits, blockIdx.z == 0 ? B.dbg : nullptr, win,
+                  (int)gridDim.x);
+}
+// Runs = categories, n <= RANK_MAX_N: the reduction and, beside it, the merge of the runs into the score order.
+// grid.x = n_runs + ceil(n_max / ORDER_THREADS).  Workgroups [0, n_runs) reduce one run each (dispatched first: they
+// are the long ones and keep their CUs for the whole launch); every other workgroup ranks ORDER_THREADS entries on a CU
+// the reduction leaves idle.  Neither kind reads what the other writes and nothing crosses workgroups: the finalize
+// launch, the first reader of order[], blk_cnt and the "not in order" words, is the join.
+__global__ __launch_bounds__(RED_THREADS) void nms_reduce_order_kernel(const NmsBatch B) {
+  const NmsImg& I = B.img[blockIdx.z];
+  __shared__ u64 win[RED_WIN_WORDS];
+  const int n_runs = B.runs.n_runs;
+  if ((int)blockIdx.x < n_runs) {  // uniform
+    nms_reduce_body(I.w.mask, I.w.diagT, I.w.w1T, I.w.w2T, I.cls_s, I.n, I.wcap, I.mpc, I.w.seg_start, B.runs, true,
+                    I.w.counters, I.w.keepbits, blockIdx.z == 0 ? B.dbg : nullptr, win, n_runs);
+  } else {
+    uint32_t* keys_s = reinterpret_cast<uint32_t*>(win);
+    nms_runs_order_small_body<4>(nullptr, I.scores, I.n, B.runs, I.w.order, I.w.rankpos, I.w.cls_s, nullptr, nullptr, 0,
+                                 I.w.blk_cnt, 2 * (I.n / 1024 + 2), I.w.run_cnt + 16, 0, keys_s, keys_s + RANK_MAX_N,
+                                 (int)blockIdx.x - n_runs, (int)gridDim.x - n_runs, true);
+  }
 }
 __global__ __launch_bounds__(FIN_THREADS) void nms_finalize_direct_kernel(const NmsBatch B) {
   const NmsImg& I = B.img[blockIdx.z];
@@ -1904,7 +1973,9 @@ static MaskThr mask_thr(double thr) {
 }
 
 // mask + reduction of the images in B (every image already has its segment-ordered box records)
-static int nms_mask_reduce(NmsBatch& B, int rotated, bool any_cls, hipStream_t s) {
+// order_beside (runs = categories, small path): the reduction launch also merges the runs into order[]
+static int nms_mask_reduce(NmsBatch& B, int rotated, bool any_cls, hipStream_t s, bool order_beside = false,
+                           int n_max = 0) {
   int nb_max = 0, wcap_max = 0;
   for (int k = 0; k < B.count; k++) {
     nb_max = std::max(nb_max, (B.img[k].n + 63) / 64);
@@ -1941,7 +2012,11 @@ static int nms_mask_reduce(NmsBatch& B, int rotated, bool any_cls, hipStream_t s
     D2_HIP_OK(hipMemsetAsync(B.dbg, 0, 256 * 8, s));
   }
   const bool timed_red = timing_begin("nms_reduce", s);
-  hipLaunchKernelGGL(nms_reduce_kernel, dim3(rgrid, 1, B.count), dim3(RED_THREADS), (size_t)wcap_max * 8, s, B);
+  if (order_beside)
+    hipLaunchKernelGGL(nms_reduce_order_kernel, dim3(B.runs.n_runs + cdiv(n_max, ORDER_THREADS), 1, B.count),
+                       dim3(RED_THREADS), (size_t)wcap_max * 8, s, B);
+  else
+    hipLaunchKernelGGL(nms_reduce_kernel, dim3(rgrid, 1, B.count), dim3(RED_THREADS), (size_t)wcap_max * 8, s, B);
   if (timed_red) timing_end("nms_reduce", s);
   D2_LAUNCH_OK();
   if (red_stamps) {
@@ -1972,11 +2047,21 @@ static int nms_run_small(NmsBatch& B, int rotated, hipStream_t s) {
   // pre-sorted runs: the order comes from one scan + one binary-search kernel.  (Runs + the caller's class ids on
   // this path would still need the class-major positions: the brute-force ranking below provides both.)
   const bool by_runs = B.runs.n_runs > 0 && (B.runs.are_cls || !any_cls);
-  if (by_runs) {  // scan + rank + records + zeroing: one launch
+  // Runs = categories (the RPN, the inference chain): records + zeroing, mask, reduction WITH the order merged beside
+  // it, finalize -- mask and reduction never read the order, so it does not run in front of them.
+  // D2AMD_NMS_ORDER_FIRST (test switch, read per call so that one process can compare both): the earlier sequence,
+  // order + records + zeroing in one launch in front of the mask.
+  const bool order_beside = by_runs && B.runs.are_cls && getenv("D2AMD_NMS_ORDER_FIRST") == nullptr;
+  if (by_runs) {
     B.order_flags = 1;
-    const dim3 ogrid(cdiv(n_max, ORDER_THREADS), 1, B.count);
-    if (rotated) hipLaunchKernelGGL((nms_runs_order_small_kernel<5>), ogrid, dim3(ORDER_THREADS), 0, s, B);
-    else hipLaunchKernelGGL((nms_runs_order_small_kernel<4>), ogrid, dim3(ORDER_THREADS), 0, s, B);
+    if (order_beside) {  // records + zeroing only
+      if (rotated) hipLaunchKernelGGL((nms_runs_records_kernel<5>), ngrid, dim3(T), 0, s, B);
+      else hipLaunchKernelGGL((nms_runs_records_kernel<4>), ngrid, dim3(T), 0, s, B);
+    } else {  // scan + rank + records + zeroing: one launch
+      const dim3 ogrid(cdiv(n_max, ORDER_THREADS), 1, B.count);
+      if (rotated) hipLaunchKernelGGL((nms_runs_order_small_kernel<5>), ogrid, dim3(ORDER_THREADS), 0, s, B);
+      else hipLaunchKernelGGL((nms_runs_order_small_kernel<4>), ogrid, dim3(ORDER_THREADS), 0, s, B);
+    }
     D2_LAUNCH_OK();
     any_cls = B.runs.are_cls != 0;
   } else {
@@ -1995,7 +2080,7 @@ static int nms_run_small(NmsBatch& B, int rotated, hipStream_t s) {
     D2_LAUNCH_OK();
   }
   }
-  const int rc = nms_mask_reduce(B, rotated, any_cls, s);
+  const int rc = nms_mask_reduce(B, rotated, any_cls, s, order_beside, n_max);
   if (rc != D2AMD_OK) return rc;
   if (by_runs && B.runs.are_cls)  // class-major position == row: order[r] is also the kept bit's position
     hipLaunchKernelGGL(nms_finalize_direct_kernel, dim3(cdiv(n_max, FIN_THREADS), 1, B.count), dim3(FIN_THREADS), 0, s, B);
