@@ -177,6 +177,10 @@ _SIGNATURES = {
                                           _vp]),
     "d2amd_fast_rcnn_loss_backward": (_i, [_vp] * 9 + [_i] * 8 + [_vp, _i, _f, ctypes.POINTER(_f), _f, _vp, _sz, _vp, _vp,
                                            _vp]),
+    "d2amd_sem_seg_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "d2amd_sem_seg_loss_forward": (_i, [_vp, _vp] + [_i] * 7 + [_i64, _vp, _vp, _vp, _sz, _vp]),
+    "d2amd_sem_seg_loss_backward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_i64, _vp, _vp]),
+    "d2amd_sem_seg_labels": (_i, [_vp] + [_i] * 11 + [_vp, _vp]),
     "d2amd_deform_conv_workspace_bytes":(_sz, [ctypes.POINTER(DcnParams), _i]),
     "d2amd_deform_conv_forward": (_i, [ctypes.POINTER(DcnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_deform_conv_backward": (_i, [ctypes.POINTER(DcnParams)] + [_vp] * 11 + [_sz, _vp]),

@@ -44,6 +44,7 @@ SOURCES = {
     "dense_loss.hip": [],
     "box_loss.hip": ["-ffp-contract=off"],
     "box_head.hip": ["-ffp-contract=off"],
+    "sem_seg.hip": ["-ffp-contract=off"],
     "polygon_masks.hip": ["-ffp-contract=off"],
     "layout.hip": [],
 }

@@ -29,6 +29,9 @@ What is bound, and what it replaces (reference file:line under the Detectron2 tr
   meta_arch/retinanet.py:160-210 RetinaNet.losses, proposal_generator/rpn.py:366-429 RPN.losses -> the fused dense-anchor
       losses (one forward and one backward launch for all images and levels, no host read; smooth_l1 / giou, 4-column
       boxes, device tensors -- anything else stays the reference's method)
+  meta_arch/semantic_seg.py:255-267 SemSegFPNHead.losses                   -> the fused upsampling + cross-entropy
+      (`sem_seg_loss`: no full-res logits; common_stride 2 / 4 / 8, <= 256 classes, device tensors -- anything else stays
+      the reference's method).  The inference side, `sem_seg_labels`, replaces three lines of the caller: INTEGRATION.md
   roi_heads/fast_rcnn.py:307-352 FastRCNNOutputLayers.losses               -> the fused box-head loss (`fast_rcnn_losses`: no
       argmax / nonzero / gather, no host read), ONLY when `only` names "box_loss": it is not part of the default set
 
@@ -127,7 +130,7 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
           only: Optional[Iterable[str]] = None) -> Patched:
     """Bind `detectron2` (default: the imported package) to this library; see the module docstring.  `models`: already
     built models whose ROIPooler instances are converted in place.  `only`: a subset of the fused bindings
-    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "dense", "dense_loss"} (default: all of them), and "box_loss", which is bound
+    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "sem_seg", "dense", "dense_loss"} (default: all of them), and "box_loss", which is bound
     only when named here."""
     want = lambda k: only is None or k in set(only)
     if detectron2 is None:
@@ -305,6 +308,24 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
 
         h._set(kh, "keypoint_rcnn_loss", keypoint_rcnn_loss)
         h._set(kh, "keypoint_rcnn_inference", keypoint_rcnn_inference)
+
+    # ---- semantic-segmentation head: SemSegFPNHead.losses (semantic_seg.py:255-267), upsampling + cross-entropy fused
+    try:
+        ss = imp("modeling.meta_arch.semantic_seg")
+    except ImportError:  # (a trimmed package without the semantic head)
+        ss = None
+    if ss is not None and want("sem_seg"):
+        ref_sem_seg_losses = ss.SemSegFPNHead.losses
+
+        def sem_seg_losses(self, predictions, targets):
+            from .modeling.sem_seg import MAX_CLASSES, SCALES
+
+            if not predictions.is_cuda or self.common_stride not in SCALES or predictions.shape[1] > MAX_CLASSES:
+                return ref_sem_seg_losses(self, predictions, targets)
+            return {"loss_sem_seg": M.sem_seg_loss(predictions, targets, common_stride=self.common_stride,
+                                                   ignore_value=self.ignore_value, loss_weight=self.loss_weight)}
+
+        h._set(ss.SemSegFPNHead, "losses", sem_seg_losses)
 
     # ---- RetinaNet inference: per-level threshold + top-k + decode and the per-class NMS of the batch in one device
     # pipeline (retinanet.py:257-309, dense_detector.py:186-260: a Python loop over images x levels with a nonzero / topk /

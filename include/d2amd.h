@@ -749,6 +749,39 @@ int d2amd_fast_rcnn_loss_backward(const void* scores, const void* deltas, const 
                                   const float* weights, float scale_clamp, const void* workspace,
                                   size_t workspace_bytes, void* grad_scores, void* grad_deltas, void* stream);
 
+/* ---- Semantic-segmentation head glue (SemSegFPNHead / SemanticSegmentor), fused.  Replaces
+ * modeling/meta_arch/semantic_seg.py:255-267 (SemSegFPNHead.losses: .float(), F.interpolate x s, F.cross_entropy),
+ * :241-243 (the upsampling at inference) and modeling/postprocessing.py:77-100 (sem_seg_postprocess) with the caller's
+ * argmax(dim=0).  No [N, C, s h, s w] tensor is allocated or written by any entry.
+ *   logits [N, C, h, w] `dtype`, `layout` D2AMD_NCHW or D2AMD_NHWC (channels_last); s = the head's common_stride.
+ *   D2AMD_EUNSUPPORTED, nothing launched: s not in {2, 4, 8}, C > 256, an unknown dtype / layout.  EINVAL: a null pointer,
+ *   an empty shape, N C h w or N s h s w >= 2^31, a short or misaligned workspace.
+ * loss forward: targets int64 [N, s h, s w].  loss_out fp32 [1] = sum over the pixels that count of (logsumexp_c(v) -
+ *   v[target]) / their number, v = the bilinear x s upsampling (align_corners=False) of the logits in fp32: the value of
+ *   F.cross_entropy(F.interpolate(x.float(), scale_factor=s, mode="bilinear", align_corners=False), t, reduction="mean",
+ *   ignore_index=ignore_value); nothing counts -> NaN, as there.  stats_out int64 [2] = (pixels that count, pixels whose
+ *   target is neither ignore_value nor in [0, C): torch device-asserts on those, here they are ignored and counted).
+ *   workspace: d2amd_sem_seg_loss_workspace_bytes(N, h, w, s) bytes, 8-byte aligned: the count, one record per workgroup
+ *   and lse of every full-res pixel (4 B each: O(N s h s w), independent of C).  The records are added in fp64 in a
+ *   fixed order: two runs are bit-identical.  Everything stays on the device.
+ * loss backward: grad_loss a DEVICE fp32 scalar; `workspace` is the forward's, unchanged; same targets / ignore_value.
+ *   grad_logits [N, C, h, w], `dtype` and `layout` of the logits, every element written exactly once (no zero fill, no
+ *   atomics): grad_loss / count * sum over the counting full-res pixels in the low-res pixel's footprint of w_y w_x
+ *   (softmax_c - [c == target]); count == 0 -> zeros.  Deterministic.
+ * labels: (ih, iw) <= (s h, s w) the image's size inside the padded prediction, (oh, ow) the output size.  labels int64
+ *   [N, oh, ow] = argmax over the classes of sem_seg_postprocess(F.interpolate(x, scale_factor=s, ...), (ih, iw), oh, ow),
+ *   both resizes composed in fp32, the lowest class among exactly equal values.  EUNSUPPORTED when a 16 x 16 output tile's
+ *   low-res footprint (about 16 ih / (oh s) + 6 rows by the same in columns) exceeds the LDS: a > 100-fold reduction. */
+size_t d2amd_sem_seg_loss_workspace_bytes(int N, int h, int w, int s);
+int d2amd_sem_seg_loss_forward(const void* logits, const int64_t* targets, int N, int C, int h, int w, int s, int dtype,
+                               int layout, int64_t ignore_value, float* loss_out, int64_t* stats_out, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int d2amd_sem_seg_loss_backward(const void* logits, const int64_t* targets, const void* workspace,
+                                const float* grad_loss, int N, int C, int h, int w, int s, int dtype, int layout,
+                                int64_t ignore_value, void* grad_logits, void* stream);
+int d2amd_sem_seg_labels(const void* logits, int N, int C, int h, int w, int s, int dtype, int layout, int ih, int iw,
+                         int oh, int ow, int64_t* labels, void* stream);
+
 /* ---- deformable convolution v1 / v2.  Replaces detectron2._C.deform_conv_forward,
  * deform_conv_backward_input, deform_conv_backward_filter, modulated_deform_conv_forward,
  * modulated_deform_conv_backward (vision.cpp:85-102; csrc/deformable/deform_conv.h:116-375).
