@@ -111,8 +111,13 @@ def _labels(x, layout, image_size, output_size, scale):
     assert 0 < ih <= scale * h and 0 < iw <= scale * w, (image_size, tuple(x.shape), scale)
     out = torch.empty((n, oh, ow), dtype=torch.int64, device=x.device)
     with _C.on_device(x.device):
-        _C.check(_C.lib().d2amd_sem_seg_labels(_C.ptr(x), n, c, h, w, scale, _C.dtype_code(x), layout, ih, iw, oh, ow,
-                                               _C.ptr(out), _C.stream()))
+        rc = _C.lib().d2amd_sem_seg_labels(_C.ptr(x), n, c, h, w, scale, _C.dtype_code(x), layout, ih, iw, oh, ow,
+                                           _C.ptr(out), _C.stream())
+    # any unsupported configuration; from Python only the refusal of a downscale whose footprint of one class exceeds
+    # the LDS reaches here (scale, classes, layout and dtype are rejected above), and it is made before any launch
+    if rc == _C.EUNSUPPORTED:
+        raise NotImplementedError(_C.lib().d2amd_last_error().decode())
+    _C.check(rc)
     return out
 
 
@@ -121,7 +126,8 @@ def sem_seg_labels(predictions: torch.Tensor, image_sizes: Sequence[Tuple[int, i
     """Label maps of a batch: for image i, argmax(dim=0) of sem_seg_postprocess(interpolate(predictions, scale_factor=s,
     bilinear, align_corners=False)[i], image_sizes[i], *output_sizes[i]) -- (N, C, h, w) stride-s logits, image_sizes the
     (height, width) of every image inside the padded batch, output_sizes the sizes wanted.  -> a list of (oh, ow) int64
-    maps, or ONE (N, oh, ow) tensor from one launch when all images share both sizes."""
+    maps, or ONE (N, oh, ow) tensor from one launch when all images share both sizes.  A downscale so heavy that the
+    low-res footprint of 16 x 16 output pixels of ONE class exceeds the LDS raises NotImplementedError."""
     _C.require_gpu(predictions, op="sem_seg_labels")
     _check_supported("sem_seg_labels", predictions, common_stride)
     n = predictions.shape[0]
