@@ -181,6 +181,8 @@ _SIGNATURES = {
     "d2amd_sem_seg_loss_forward": (_i, [_vp, _vp] + [_i] * 7 + [_i64, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_sem_seg_loss_backward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_i64, _vp, _vp]),
     "d2amd_sem_seg_labels": (_i, [_vp] + [_i] * 11 + [_vp, _vp]),
+    "d2amd_panoptic_workspace_bytes": (_sz, [_i, _i, _i]),
+    "d2amd_panoptic_combine": (_i, [_vp] * 6 + [_i] * 5 + [_f, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_deform_conv_workspace_bytes":(_sz, [ctypes.POINTER(DcnParams), _i]),
     "d2amd_deform_conv_forward": (_i, [ctypes.POINTER(DcnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_deform_conv_backward": (_i, [ctypes.POINTER(DcnParams)] + [_vp] * 11 + [_sz, _vp]),

@@ -45,6 +45,7 @@ SOURCES = {
     "box_loss.hip": ["-ffp-contract=off"],
     "box_head.hip": ["-ffp-contract=off"],
     "sem_seg.hip": ["-ffp-contract=off"],
+    "panoptic.hip": ["-ffp-contract=off"],
     "polygon_masks.hip": ["-ffp-contract=off"],
     "layout.hip": [],
 }

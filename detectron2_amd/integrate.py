@@ -32,6 +32,9 @@ What is bound, and what it replaces (reference file:line under the Detectron2 tr
   meta_arch/semantic_seg.py:255-267 SemSegFPNHead.losses                   -> the fused upsampling + cross-entropy
       (`sem_seg_loss`: no full-res logits; common_stride 2 / 4 / 8, <= 256 classes, device tensors -- anything else stays
       the reference's method).  The inference side, `sem_seg_labels`, replaces three lines of the caller: INTEGRATION.md
+  meta_arch/panoptic_fpn.py:184-269 combine_semantic_and_instance_outputs   -> the fused merge of things and stuff (four
+      launches and one host transfer for the host loop's ~350 reads; device tensors, <= 128 detections, bool / uint8
+      masks -- anything else stays the reference's function)
   roi_heads/fast_rcnn.py:307-352 FastRCNNOutputLayers.losses               -> the fused box-head loss (`fast_rcnn_losses`: no
       argmax / nonzero / gather, no host read), ONLY when `only` names "box_loss": it is not part of the default set
 
@@ -130,7 +133,7 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
           only: Optional[Iterable[str]] = None) -> Patched:
     """Bind `detectron2` (default: the imported package) to this library; see the module docstring.  `models`: already
     built models whose ROIPooler instances are converted in place.  `only`: a subset of the fused bindings
-    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "sem_seg", "dense", "dense_loss"} (default: all of them), and "box_loss", which is bound
+    {"matcher", "pooler", "rpn", "box_inference", "mask_head", "keypoint_head", "sem_seg", "panoptic", "dense", "dense_loss"} (default: all of them), and "box_loss", which is bound
     only when named here."""
     want = lambda k: only is None or k in set(only)
     if detectron2 is None:
@@ -326,6 +329,29 @@ def patch(detectron2=None, models: Iterable = (), layers: bool = True, fused: bo
                                                    ignore_value=self.ignore_value, loss_weight=self.loss_weight)}
 
         h._set(ss.SemSegFPNHead, "losses", sem_seg_losses)
+
+    # ---- Panoptic FPN merge: combine_semantic_and_instance_outputs (panoptic_fpn.py:184-269), looked up in its module by
+    # PanopticFPN.forward_inference at every call
+    try:
+        pf = imp("modeling.meta_arch.panoptic_fpn")
+    except ImportError:  # (a trimmed package without Panoptic FPN)
+        pf = None
+    if pf is not None and want("panoptic"):
+        ref_combine = pf.combine_semantic_and_instance_outputs
+
+        def combine_semantic_and_instance_outputs(instance_results, semantic_results, overlap_threshold, stuff_area_thresh,
+                                                  instances_score_thresh):
+            from .modeling.panoptic import MAX_DETECTIONS
+
+            masks = instance_results.pred_masks
+            if (not semantic_results.is_cuda or not masks.is_cuda or len(instance_results.scores) > MAX_DETECTIONS
+                    or masks.dtype not in (torch.bool, torch.uint8)):
+                return ref_combine(instance_results, semantic_results, overlap_threshold, stuff_area_thresh,
+                                   instances_score_thresh)
+            return M.combine_semantic_and_instance_outputs(instance_results, semantic_results, overlap_threshold,
+                                                           stuff_area_thresh, instances_score_thresh)
+
+        h._set(pf, "combine_semantic_and_instance_outputs", combine_semantic_and_instance_outputs)
 
     # ---- RetinaNet inference: per-level threshold + top-k + decode and the per-class NMS of the batch in one device
     # pipeline (retinanet.py:257-309, dense_detector.py:186-260: a Python loop over images x levels with a nonzero / topk /

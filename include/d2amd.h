@@ -782,6 +782,36 @@ int d2amd_sem_seg_loss_backward(const void* logits, const int64_t* targets, cons
 int d2amd_sem_seg_labels(const void* logits, int N, int C, int h, int w, int s, int dtype, int layout, int ih, int iw,
                          int oh, int ow, int64_t* labels, void* stream);
 
+/* ---- Panoptic FPN merge, fused.  Replaces modeling/meta_arch/panoptic_fpn.py:184-269
+ * (combine_semantic_and_instance_outputs: a host loop over the detections in score order with three .item() reads and
+ * about six full-image launches per detection, then torch.unique(...).cpu() and one read per stuff class) with four
+ * launches on `stream` and no host read: a one-workgroup ranking of the scores, a coverage kernel over 64 x 16 pixel
+ * tiles, the greedy pass in one workgroup, and the write of the id map.  ONE image per call.
+ *   scores fp32 [R], pred_classes int64 [R], semantic int64 [H, W] (contiguous category ids).
+ *   Mask source, exactly one non-NULL when R > 0: pred_masks uint8 / bool [R, H, W] (non-zero = covered), or mask_probs
+ *   [R, M, M] `mask_dtype` with boxes fp32 [R, 4] in output-image coordinates: then a pixel is covered exactly where
+ *   d2amd_paste_masks at `mask_threshold` (>= 0) writes 1 -- the sample is evaluated in the kernel, no [R, H, W] mask exists.
+ *   Detections are ranked by descending score, ties by lower index; candidates have (double)score >=
+ *   instances_score_thresh.  In rank order: area == 0 -> skipped; (double)intersection / (double)area >
+ *   overlap_threshold -> skipped; else the next id, owning its not yet owned pixels.  Then labels 1 .. num_classes - 1
+ *   that occur in the image, ascending: area = their pixels no thing owns, dropped iff (double)area < stuff_area_thresh.
+ *   Pixels with a label outside [0, num_classes) get no stuff segment and are counted in stats.
+ *   panoptic_seg int32 [H, W] (16-byte aligned), every pixel written.  segments int64 [R + num_classes, 5]: rows (id,
+ *   isthing, category_id, instance index or -1, area -- of a thing: after truncation) in id order, zeros behind.
+ *   count int64 [1] segments; stats int64 [1] pixels with an out-of-range label.  Integer sums: two runs are bit-identical.
+ *   workspace: d2amd_panoptic_workspace_bytes(H, W, R) bytes, 16-byte aligned -- the worst case of any input (the set
+ *   words, one 24-byte record and one overflow index per pixel); no allocation, synchronisation or host read inside.
+ *   D2AMD_EUNSUPPORTED, nothing launched: R > 128, num_classes > 256, M M 4 B > 32 KB (the LDS staging buffer), an
+ *   unknown mask_dtype.  EINVAL: an empty image, H W >= 2^31, both or neither mask source, mask_threshold < 0, a null or
+ *   misaligned pointer.  EWORKSPACE: a short workspace. */
+size_t d2amd_panoptic_workspace_bytes(int H, int W, int R);
+int d2amd_panoptic_combine(const float* scores, const int64_t* pred_classes, const int64_t* semantic,
+                           const uint8_t* pred_masks, const void* mask_probs, const float* boxes, int R, int H, int W,
+                           int M, int mask_dtype, float mask_threshold, double overlap_threshold,
+                           double stuff_area_thresh, double instances_score_thresh, int num_classes,
+                           int32_t* panoptic_seg, int64_t* segments, int64_t* count, int64_t* stats, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- deformable convolution v1 / v2.  Replaces detectron2._C.deform_conv_forward,
  * deform_conv_backward_input, deform_conv_backward_filter, modulated_deform_conv_forward,
  * modulated_deform_conv_backward (vision.cpp:85-102; csrc/deformable/deform_conv.h:116-375).
