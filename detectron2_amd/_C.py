@@ -172,6 +172,14 @@ _SIGNATURES = {
     "d2amd_dense_loss_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
                                        _i, ctypes.POINTER(_i), _i, _i, _i, _i, _f, _f, _i, _f, ctypes.POINTER(_f), _f,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "d2amd_fcos_gt_chunk": (_i, []),
+    "d2amd_fcos_loss_workspace_bytes": (_sz, [_i, ctypes.POINTER(_i), _i]),
+    "d2amd_fcos_label_anchors": (_i, [ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i, ctypes.POINTER(_i), _i, _i, _f, _vp,
+                                      _vp, _vp, _vp]),
+    "d2amd_fcos_loss_forward": (_i, [ctypes.POINTER(_vp)] * 4 + [_vp, _vp, _vp, _i, _vp, _vp, _i, ctypes.POINTER(_i), _i,
+                                     _i, _i, _f, _i, _f, _f] + [_vp] * 6 + [_sz, _vp]),
+    "d2amd_fcos_loss_backward": (_i, [ctypes.POINTER(_vp)] * 4 + [_vp, _vp, _vp, _i] + [_vp] * 6 +
+                                 [_i, ctypes.POINTER(_i), _i, _i, _i, _i, _f, _f] + [ctypes.POINTER(_vp)] * 3 + [_vp]),
     "d2amd_fast_rcnn_loss_workspace_bytes": (_sz, [_i]),
     "d2amd_fast_rcnn_loss_forward": (_i, [_vp] * 7 + [_i] * 8 + [_vp, _i, _f, ctypes.POINTER(_f), _f, _vp, _vp, _vp, _sz,
                                           _vp]),

@@ -42,6 +42,7 @@ SOURCES = {
     "mask_head.hip": [],
     "keypoint_head.hip": ["-ffp-contract=off"],
     "dense_loss.hip": [],
+    "fcos.hip": ["-ffp-contract=off"],
     "box_loss.hip": ["-ffp-contract=off"],
     "box_head.hip": ["-ffp-contract=off"],
     "sem_seg.hip": ["-ffp-contract=off"],

@@ -111,46 +111,6 @@ __device__ __forceinline__ int2 dl_stage_labels(const int64_t* __restrict__ gt_l
   return make_int2(s_cnt[0], s_cnt[1]);
 }
 
-// ---- focal / BCE term (fvcore sigmoid_focal_loss, F.binary_cross_entropy_with_logits) ---------------------------
-// GM: 0 gamma == 0, 2 gamma == 2, 1 any other gamma > 0
-__device__ __forceinline__ float dl_alpha_t(bool t, float alpha) { return alpha >= 0.f ? (t ? alpha : 1.f - alpha) : 1.f; }
-
-template <int GM> __device__ __forceinline__ float dl_focal(float x, int code, int c, const DlParams& p) {
-  const bool t = code == c;
-  const float z = t ? -x : x;
-  const float e = __expf(-fabsf(x));
-  const float l = __logf(1.f + e);
-  const float ce = fmaxf(z, 0.f) + l;
-  float mod = 1.f;
-  if (GM == 2) {
-    const float s = __builtin_amdgcn_rcpf(1.f + e);
-    const float q = z >= 0.f ? s : e * s;
-    mod = q * q;
-  } else if (GM == 1) {
-    mod = __expf(-p.gamma * (fmaxf(-z, 0.f) + l));
-  }
-  const float v = dl_alpha_t(t, p.alpha) * ce * mod;
-  return code < 0 ? 0.f : v;  // (a select: an ignored row's NaN stays out)
-}
-
-// d loss / d x, times the upstream gradient g
-template <int GM> __device__ __forceinline__ float dl_focal_grad(float x, int code, int c, const DlParams& p, float g) {
-  const bool t = code == c;
-  const float z = t ? -x : x;
-  const float e = __expf(-fabsf(x));
-  const float s = __builtin_amdgcn_rcpf(1.f + e);
-  const float q = z >= 0.f ? s : e * s, omq = z >= 0.f ? e * s : s;
-  float d = q;
-  if (GM != 0) {
-    const float l = __logf(1.f + e);
-    const float ce = fmaxf(z, 0.f) + l;
-    const float mod = GM == 2 ? q * q : __expf(-p.gamma * (fmaxf(-z, 0.f) + l));
-    d = mod * (q + p.gamma * ce * omq);
-  }
-  const float v = dl_alpha_t(t, p.alpha) * d * (t ? -g : g);
-  return code < 0 ? 0.f : v;
-}
-
 // anchor `a` of the tile (foreground) -> its box loss and delta gradient
 template <typename T>
 __device__ __forceinline__ float dl_box_row(const DlTile& t, const float* __restrict__ gt_boxes, const DlParams& p, int a,

@@ -704,6 +704,56 @@ int d2amd_dense_loss_backward(const void* const* logits, const void* const* delt
                               const float* weights, float scale_clamp, void* const* grad_logits,
                               void* const* grad_deltas, void* stream);
 
+/* ---- FCOS training head: point matching + focal / GIoU / centerness losses (csrc/fcos.hip) -------------------------
+ * One forward and one backward launch for all images and levels (meta_arch/fcos.py:97-251, Box2BoxTransformLinear of
+ * box_regression.py:230-307).  anchors[l] fp32 [A_l,4] (16-byte aligned), logits[l] [N,A_l,K], deltas[l] [N,A_l,4],
+ * ctrness[l] [N,A_l] in `dtype`; 1 <= L <= D2AMD_RPN_MAX_LEVELS, every A_l >= 1, R = sum A_l.
+ * Targets, one of:
+ *   packed ground truth: gt_boxes fp32 [G,4] (16-byte aligned), gt_classes int64 [G], gt_offsets int32 [N+1] ON THE
+ *     DEVICE (image n owns rows gt_offsets[n] .. gt_offsets[n+1]; values are clamped to [0, G]); gt_labels and
+ *     matched_boxes NULL.  The forward matches inside the loss kernel and writes matched int32 [N,R] (index inside the
+ *     image's rows, -1 background), which is all the backward needs.
+ *   given: gt_labels int64 [N,R] (a class in [0,K) is positive, anything else background) and matched_boxes fp32
+ *     [N,R,4] (16-byte aligned, read for positive points); the packed pointers and `matched` are ignored.
+ * Matching, in fp32 in the reference's operation order: point p = anchor centre, size = x2 - x1 of the anchor; box m
+ *   passes if max(|p - centre_m|) < radius * size, min(l,t,r,b) > 0 and lower < max(l,t,r,b) < upper with lower = 4 size
+ *   (0 on level 0) and upper = 8 size (+inf on level L-1); the winner has the largest quality 1e8f - area_m, the lowest
+ *   index among equal qualities; a quality < 1e-5 never matches.  The ground truth is staged in LDS
+ *   D2AMD_FCOS_GT_CHUNK boxes at a time (any G is served).
+ * Losses (SUMS: the caller divides by its normalizer): sigmoid focal over all N R K logits (alpha < 0: no weighting;
+ *   gamma >= 0); on positive points GIoU (eps 1e-7) of the box (cx - l, cy - t, cx + r, cy + b), (l,t,r,b) =
+ *   relu(delta) [* anchor size when normalize_by_size], against the matched box, and BCE-with-logits of the centerness
+ *   logit against sqrt(min(l,r)/max(l,r) * min(t,b)/max(t,b)) of the matched box's distances.
+ * forward: three fp32 device scalars and stats int64[2] = (#positive points, N R).  workspace:
+ *   d2amd_fcos_loss_workspace_bytes bytes, 8-byte aligned, one record per tile of 256 points, added in fp64 in a fixed
+ *   order: two runs are bit-identical.
+ * backward: grad_cls / grad_loc / grad_ctr are DEVICE fp32 scalars; every element of grad_logits[l], grad_deltas[l]
+ *   (aligned to a row of four) and grad_ctrness[l] is written once, zeros included (background rows, deltas <= 0).
+ * d2amd_fcos_label_anchors: the matching alone -> labels int64 [N,R] (class of the matched box, num_classes for
+ *   background), boxes fp32 [N,R,4] (the matched box; the image's box 0 for an unmatched point, zeros for an image
+ *   without ground truth: FCOS.label_anchors), matched int32 [N,R] when not NULL.
+ * EINVAL before any launch: bad shapes (L above the maximum, an empty level), null or misaligned pointers, gamma < 0,
+ *   alpha > 1, an unknown dtype, a short workspace.  Nothing synchronises with the host. */
+#define D2AMD_FCOS_GT_CHUNK 128
+int d2amd_fcos_gt_chunk(void);
+size_t d2amd_fcos_loss_workspace_bytes(int N, const int* level_anchors, int L);
+int d2amd_fcos_label_anchors(const float* const* anchors, const float* gt_boxes, const int64_t* gt_classes,
+                             const int* gt_offsets, int G, int N, const int* level_anchors, int L, int num_classes,
+                             float radius, int64_t* labels_out, float* boxes_out, int* matched_out, void* stream);
+int d2amd_fcos_loss_forward(const void* const* logits, const void* const* deltas, const void* const* ctrness,
+                            const float* const* anchors, const float* gt_boxes, const int64_t* gt_classes,
+                            const int* gt_offsets, int G, const int64_t* gt_labels, const float* matched_boxes, int N,
+                            const int* level_anchors, int L, int K, int dtype, float radius, int normalize_by_size,
+                            float alpha, float gamma, int* matched_out, float* loss_cls_sum, float* loss_loc_sum,
+                            float* loss_ctr_sum, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+int d2amd_fcos_loss_backward(const void* const* logits, const void* const* deltas, const void* const* ctrness,
+                             const float* const* anchors, const float* gt_boxes, const int64_t* gt_classes,
+                             const int* gt_offsets, int G, const int* matched, const int64_t* gt_labels,
+                             const float* matched_boxes, const float* grad_cls, const float* grad_loc,
+                             const float* grad_ctr, int N, const int* level_anchors, int L, int K, int dtype,
+                             int normalize_by_size, float alpha, float gamma, void* const* grad_logits,
+                             void* const* grad_deltas, void* const* grad_ctrness, void* stream);
+
 /* ---- Box-head training loss (Fast R-CNN classification + box regression), fused.  Replaces
  * modeling/roi_heads/fast_rcnn.py:307-352 (FastRCNNOutputLayers.losses) with :88-115 (_log_classification_stats),
  * :386-422 (sigmoid_cross_entropy_loss) and :424-463 (box_reg_loss): no argmax / nonzero / gather launches, no host read.
