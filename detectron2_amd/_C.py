@@ -110,6 +110,9 @@ _SIGNATURES = {
     "d2amd_match_boxes_batch_workspace_bytes": (_sz, [ctypes.POINTER(_i), _i]),
     "d2amd_match_boxes_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _vp, _i, ctypes.POINTER(_f),
                                      ctypes.POINTER(ctypes.c_int8), _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "d2amd_match_boxes_rotated_batch_workspace_bytes": (_sz, [ctypes.POINTER(_i), _i, _i]),
+    "d2amd_match_boxes_rotated_batch": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _vp, _i, ctypes.POINTER(_f),
+                                             ctypes.POINTER(ctypes.c_int8), _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "d2amd_label_and_sample_max_candidates": (_i, []),
     "d2amd_label_and_sample_proposals": (_i, [ctypes.POINTER(SampleImage), _i, ctypes.POINTER(_f),
                                               ctypes.POINTER(ctypes.c_int8), _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp,
@@ -172,6 +175,12 @@ _SIGNATURES = {
     "d2amd_dense_loss_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
                                        _i, ctypes.POINTER(_i), _i, _i, _i, _i, _f, _f, _i, _f, ctypes.POINTER(_f), _f,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "d2amd_rrpn_loss_workspace_bytes": (_sz, [_i, ctypes.POINTER(_i), _i]),
+    "d2amd_rrpn_loss_forward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _i,
+                                     ctypes.POINTER(_i), _i, _i, _f, ctypes.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d2amd_rrpn_loss_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
+                                      _i, ctypes.POINTER(_i), _i, _i, _f, ctypes.POINTER(_f), ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), _vp]),
     "d2amd_fcos_gt_chunk": (_i, []),
     "d2amd_fcos_loss_workspace_bytes": (_sz, [_i, ctypes.POINTER(_i), _i]),
     "d2amd_fcos_label_anchors": (_i, [ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i, ctypes.POINTER(_i), _i, _i, _f, _vp,

@@ -33,6 +33,7 @@ SOURCES = {
     "dcn_gemm.hip": [],
     "dcn_colpath.hip": [],
     "matcher.hip": ["-ffp-contract=off"],
+    "matcher_rot.hip": ["-ffp-contract=off"],
     "label_sample.hip": ["-ffp-contract=off"],
     "subsample.hip": ["-ffp-contract=off"],
     "random_keys.hip": [],
@@ -42,6 +43,7 @@ SOURCES = {
     "mask_head.hip": [],
     "keypoint_head.hip": ["-ffp-contract=off"],
     "dense_loss.hip": [],
+    "rrpn_loss.hip": ["-ffp-contract=off"],
     "fcos.hip": ["-ffp-contract=off"],
     "box_loss.hip": ["-ffp-contract=off"],
     "box_head.hip": ["-ffp-contract=off"],

@@ -347,6 +347,24 @@ int d2amd_match_boxes_batch(const float* const* gt_boxes, const int* M, int coun
 int d2amd_match_quality_matrix(const float* quality, int M, int N, const float* thresholds,
                                const int8_t* labels, int T, int allow_low_quality, int64_t* matches,
                                int8_t* match_labels, void* workspace, size_t workspace_bytes, void* stream);
+/* The ROTATED form: Matcher.__call__ fused with pairwise_iou_rotated (structures/rotated_boxes.py:483-503), as
+ * proposal_generator/rrpn.py:151-200 calls them once per image -- the M x N matrix (more than 99 % exact zeros for RRPN
+ * anchors) is never written.  gt_boxes (host array of `count` device pointers) [M[i]][5], boxes [N][5] fp32 rows
+ * (cx, cy, w, h, angle in degrees), M (host) [count]; thresholds / labels / T / allow_low_quality as above; outputs
+ * matches [count][N] int64, match_labels [count][N] int8; the single-image form is count = 1.  An image with M[i] == 0
+ * gets index 0 and labels[0].  Bit-exact with d2amd_box_iou_rotated (ground truth = boxes1) + d2amd_match_quality_matrix
+ * for FINITE boxes, zero-area and tiny ones included: first maximal index, every tie of a row maximum gets the
+ * low-quality label, a ground-truth box that overlaps nothing (row maximum 0) marks every box of quality 0.  Non-finite
+ * coordinates are outside the contract (they cannot make the kernel index outside its LDS, but the result is unspecified).
+ * workspace: d2amd_match_boxes_rotated_batch_workspace_bytes(M, count, N) bytes, 16-byte aligned (row maxima and one
+ * 4-byte column-maximum key per box and image, used only with allow_low_quality; too small: D2AMD_EINVAL before any
+ * launch).  Two launches with allow_low_quality (the second recomputes the overlapping pairs of the boxes whose best
+ * quality reaches a row maximum), one without; nothing is read on the host. */
+size_t d2amd_match_boxes_rotated_batch_workspace_bytes(const int* M, int count, int N);
+int d2amd_match_boxes_rotated_batch(const float* const* gt_boxes, const int* M, int count, const float* boxes, int N,
+                                    const float* thresholds, const int8_t* labels, int T, int allow_low_quality,
+                                    int64_t* matches, int8_t* match_labels, void* workspace, size_t workspace_bytes,
+                                    void* stream);
 
 /* ---- RPN / RetinaNet proposal selection in front of NMS, all images and feature levels in one call.
  * Replaces proposal_generator/rpn.py:468-533 (_decode_proposals), modeling/box_regression.py:71-116
@@ -703,6 +721,35 @@ int d2amd_dense_loss_backward(const void* const* logits, const void* const* delt
                               int label_mode, float alpha, float gamma, int box_loss, float smooth_l1_beta,
                               const float* weights, float scale_clamp, void* const* grad_logits,
                               void* const* grad_deltas, void* stream);
+
+/* ---- Rotated proposal generator (RRPN) training losses: objectness BCE + rotated box regression, all images and levels
+ * in ONE forward and ONE backward launch (csrc/rrpn_loss.hip).  Replaces proposal_generator/rpn.py:366-429 (RPN.losses as
+ * RRPN inherits it) with box_regression.py:145-181 (Box2BoxTransformRotated.get_deltas) and fvcore's smooth_l1_loss.
+ *   logits[l] [N, A_l] and deltas[l] [N, A_l, 5] contiguous, `dtype` (device pointers in host arrays);
+ *   anchors[l] fp32 [A_l, 5] rows (cx, cy, w, h, angle in degrees); level_anchors (host) [L] = A_l, L <= 8;
+ *   gt_labels int8 [N, R]: -1 ignore, 0 background, 1 foreground, any other value is ignored; gt_boxes fp32 [N, R, 5];
+ *   R = sum A_l, levels in order.  weights (host) [5] = (wx, wy, ww, wh, wa), positive.
+ *   box term on the foreground rows, targets in fp64: wx (tcx - cx) / w, wy (tcy - cy) / h, ww log(tw / w),
+ *   wh log(th / h), wa pi / 180 (((ta - a + 180) mod 360) - 180) with torch's floor-mod (a difference of exactly +-180
+ *   degrees gives -180); smooth-L1 of (delta - target), smooth_l1_beta < 1e-5 is L1.
+ * forward: loss_cls_sum, loss_box_sum fp32 scalars (SUMS: the caller divides), stats int64[2] = (#foreground rows,
+ *   #valid rows), on the device.  workspace: d2amd_rrpn_loss_workspace_bytes(N, level_anchors, L) bytes, 8-byte aligned,
+ *   one record per tile of 256 anchors, added in fp64 in a fixed order: two runs are bit-identical.
+ * backward: grad_cls, grad_box are DEVICE fp32 scalars; grad_logits[l] / grad_deltas[l] (`dtype`, shapes of the inputs) are
+ *   written completely: zeros for ignored rows and for the deltas of rows that are not foreground.
+ * Negative sizes, more than 8 levels, a dtype code outside F32 / F16 / BF16, a null pointer, non-positive weights or a
+ * short workspace: D2AMD_EINVAL before any launch.  No tile (N == 0, L == 0 or only empty levels): D2AMD_OK, nothing is
+ * launched and no output is written. */
+size_t d2amd_rrpn_loss_workspace_bytes(int N, const int* level_anchors, int L);
+int d2amd_rrpn_loss_forward(const void* const* logits, const void* const* deltas, const float* const* anchors,
+                            const int8_t* gt_labels, const float* gt_boxes, int N, const int* level_anchors, int L,
+                            int dtype, float smooth_l1_beta, const float* weights, float* loss_cls_sum,
+                            float* loss_box_sum, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+int d2amd_rrpn_loss_backward(const void* const* logits, const void* const* deltas, const float* const* anchors,
+                             const int8_t* gt_labels, const float* gt_boxes, const float* grad_cls,
+                             const float* grad_box, int N, const int* level_anchors, int L, int dtype,
+                             float smooth_l1_beta, const float* weights, void* const* grad_logits,
+                             void* const* grad_deltas, void* stream);
 
 /* ---- FCOS training head: point matching + focal / GIoU / centerness losses (csrc/fcos.hip) -------------------------
  * One forward and one backward launch for all images and levels (meta_arch/fcos.py:97-251, Box2BoxTransformLinear of
